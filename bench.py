@@ -2,6 +2,8 @@
 """bench.py -- env-steps/s of the batched Space Fortress env.step() on MI355X.
 
     python bench.py --gpus 1 --steps 2000 --warmup 100
+    python bench.py --gpus 1 --steps 2000 --warmup 100 --full    ... and every other figure listed below
+    python bench.py --gpus 1 --steps 2000 --warmup 100 --dump-outputs DIR
     python bench.py --gpus N ...          N > 1 without WORLD_SIZE: bench.py starts the N ranks itself (fresh child
                                           processes, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set; rl/train.py:30-32 starts
                                           its N workers from one command too)
@@ -12,10 +14,18 @@ with action decoding, reward shaping, the 19-float observation and auto-reset.  
 BASELINE.json's metric config -- youturn, 65 536 envs per GPU, features obs (f32), uniform
 random discrete actions pre-generated in HBM (a ring of 64 action batches).  N > 1: one
 process per GPU, each with its own 65 536-lane shard (weak scaling, no data-path
-collective); RCCL all-gathers the 8-element episode-statistics vector once, after the
-timed region.
+collective).
 
-The JSON line also carries
+A plain run sets up, warms up, times exactly --steps launches (one block unless --repeats asks
+for more; no HIP events inside),
+writes the last step's outputs if --dump-outputs is given, and prints the JSON line: value,
+ms_per_step and the rest of the headline.  --dump-outputs DIR writes what that last timed step
+returned to its caller (env.step_tensors: obs, reward, done, info) as DIR/<name>.npy in float32 /
+float64; the actions and the initial states are seeded, so the same arguments give the same files.
+
+With --full the timed steps are --repeats blocks of --steps launches (the median block is the
+headline), every other one carrying a pair of HIP events; RCCL all-gathers the 8-element
+episode-statistics vector once, after the timed region; and the JSON line also carries
   roofline      the step kernel against the HBM roofline: algorithmic bytes per launch
                 (464 B/env-step youturn, 408 autoturn) / mean launch duration,
                 measured here with HIP events on the launch stream;
@@ -49,6 +59,7 @@ ALGO_BYTES = {"youturn": 464, "autoturn": 408, "test-youturn": 464, "test-autotu
 IMAGE_ALGO_BYTES = 7448  # one new 84x84 frame instead of the feature row
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
 METRIC = "env-steps/sec (whole node), youturn random-action rollout @65536 envs/GPU"
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: array bytes of all files together (64 MB with the .npy headers to spare)
 
 
 def cpu_baseline(gametype, seconds, cores):
@@ -254,6 +265,31 @@ def whole_job_value(ranks, elapsed_s):
     return sum(r["value_share"] for r in ranks)
 
 
+def dump_outputs(outdir, outs, suffix, budget):
+    """--dump-outputs: (obs, reward, done, info) as the last timed step left them -> outdir/<name><suffix>.npy.  obs keeps
+    float32 / float64 (an image batch's uint8 frames become float32), reward (int32) becomes float64, done / info float32:
+    every value exact.  A batch whose arrays would pass `budget` bytes is cut to a fixed, seeded sample of lanes, the same
+    for every array, whose indices go to lanes<suffix>.npy."""
+    import numpy as np
+    import torch
+
+    obs, rew, done, info = outs
+    obs_f = torch.float64 if obs.dtype == torch.float64 else torch.float32
+    n = obs.shape[0]
+    row = obs[0].numel() * (8 if obs_f == torch.float64 else 4) + 8 + 4 + 4 + 8  # (the 8 of lanes.npy counted too)
+    arrays = {}
+    if n * row > budget:
+        lanes = np.sort(np.random.default_rng(0).choice(n, budget // row, replace=False))
+        pick = torch.from_numpy(lanes).to(obs.device)
+        obs, rew, done, info = (t.index_select(0, pick) for t in (obs, rew, done, info))
+        arrays["lanes"] = lanes.astype(np.float64)
+    arrays.update(obs=obs.to(obs_f).cpu().numpy(), reward=rew.to(torch.float64).cpu().numpy(),
+                  done=done.to(torch.float32).cpu().numpy(), info=info.to(torch.float32).cpu().numpy())
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + suffix + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -261,7 +297,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=0,
                     help="timed blocks of --steps launches each, every one bracketed by barrier + synchronize; the line "
-                         "reports the MEDIAN block (0 = enough blocks for about 2000 launches in all, at most 101)")
+                         "reports the MEDIAN block (0 = one block, so that the run times exactly --steps launches; with --full, "
+                         "enough blocks for about 2000 launches in all, at most 101)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the CPU baseline, HIP events on every other timed block and the "
+                         "roofline, the sampled-action and loop-issued blocks, the steady-state loop and the episode-statistics "
+                         "reduction, per-launch event timing, the fused rollout, the copy ceiling, the image config, the other "
+                         "configurations and the host API.  Without it a run sets up, warms up, times its steps, writes "
+                         "--dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (obs, reward, done, info) as DIR/<name>.npy "
+                         "in float32 / float64, at most 64 MB in all (a fixed, seeded sample of lanes beyond that); one "
+                         "set per rank (<name>_rank<r>.npy) when --gpus > 1")
     ap.add_argument("--launch", choices=("auto", "loop", "graph"), default="auto",
                     help="how a timed block's K sf_step launches are issued: one by one from Python (loop) or as ONE HIP graph "
                          "captured once and replayed per block (graph); auto = graph for K <= 512.  A block of a few launches "
@@ -299,6 +346,9 @@ def main():
         args.no_configs = args.no_cpu_baseline = True
         args.steady_seconds = 0.0
         args.kernel_timing_launches = 1
+    if not args.full:  # (the legs that have switches of their own; the others are under `if args.full` below)
+        args.rollout_k = args.numpy_api = args.image_envs = 0
+        args.no_configs = args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and not os.environ.get("SF_BENCH_NO_SPAWN"):
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], args))
@@ -339,7 +389,7 @@ def main():
     # the job is ONE batch of world * n lanes cut into contiguous shards: rank r's lane i is lane r*n + i of the whole
     # batch and takes that stretch of the spawn stream (spawn_stride 1), so N ranks equal one N*n-lane batch
     lane0, lane1 = shard_lanes(n * world, world, rank)
-    repeats = args.repeats or max(1, min(101, -(-2000 // max(1, args.steps))))
+    repeats = args.repeats or (max(1, min(101, -(-2000 // max(1, args.steps)))) if args.full else 1)
 
     def gather_ranks(mine):
         if dist is None:
@@ -423,7 +473,7 @@ def main():
     # thread is the classic "operation not permitted when stream is capturing"; replays are ordinary launches.
     # Every block replays the same K action rows on the state the previous block left, so episodes still progress.
     graph = capture(lambda k: step(act_rows[k % ring]), K) if use_graph else None
-    graph_sampled = capture(lambda k: step_sampled(), K) if use_graph else None
+    graph_sampled = capture(lambda k: step_sampled(), K) if use_graph and args.full else None
 
     if dist is not None:
         dist.init_process_group("nccl", device_id=dev)
@@ -443,10 +493,11 @@ def main():
         around its launches: they measure the launch period on the GPU's clock for `roofline`, and they cost the block 7 us
         of its own (two barrier packets on the stream and their completion: tools/block_probe.py, 155.5 against 148.0 us at
         K = 20) -- so `value` comes from the blocks WITHOUT them, which hold the K launches between the brackets and nothing
-        else, and the event blocks' own median is reported beside it (block_ms.with_events_median)."""
+        else, and the event blocks' own median is reported beside it (block_ms.with_events_median).  Without --full no
+        block carries them."""
         blocks, own, periods, with_ev = [], [], [], []
         for rep in range(reps):
-            evs = reps == 1 or rep % 2 == 1
+            evs = args.full and (reps == 1 or rep % 2 == 1)
             barrier()
             t0 = time.perf_counter()
             if graph_ is not None:
@@ -497,57 +548,62 @@ def main():
     blocks, own_blocks, periods, with_ev = timed_blocks(graph, launch_ring, repeats)
     tpos[0] += K * repeats
     env.check_state()  # after the timed blocks (every rank its own shard)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, env._bufs,  # (reuse_buffers: every step writes into these four tensors)
+                     "_rank%d" % rank if world > 1 else "", DUMP_BYTES // world)
     med, order = pick(blocks, with_ev)
     elapsed = blocks[med]
     ev_blocks = sorted(blocks[r] for r in range(repeats) if with_ev[r])
-    # mean launch-to-launch time of sf_step_kernel over the blocks that carried the HIP events (their median; end of the first
-    # launch to end of the last): the launches are back to back on one stream, so this is the kernel duration plus the
-    # dependent-launch gap -- a launch PERIOD
-    region_ms = sorted(periods)[len(periods) // 2]
+    steady_ms = None
+    if args.full:
+        # mean launch-to-launch time of sf_step_kernel over the blocks that carried the HIP events (their median; end of the first
+        # launch to end of the last): the launches are back to back on one stream, so this is the kernel duration plus the
+        # dependent-launch gap -- a launch PERIOD
+        region_ms = sorted(periods)[len(periods) // 2]
 
-    # ---- the same blocks with the actions drawn inside the launch (sf_step_sampled)
-    s_reps = 1 if args.timed_only else repeats
-    s_blocks, _, s_periods, s_ev = timed_blocks(graph_sampled, lambda t: step_sampled(), s_reps)
-    s_med, _ = pick(s_blocks, s_ev)
-    s_period = sorted(s_periods)[len(s_periods) // 2]
-    # ---- ... and, when the blocks above were HIP graphs, a few blocks issued one by one from Python: the per-call host path
-    loop_issue = None
-    if graph is not None and not args.timed_only:
-        l_blocks, _, l_periods, l_ev = timed_blocks(None, launch_ring, max(4, repeats // 8))
-        l_med, _ = pick(l_blocks, l_ev)
-        loop_issue = {"value": float(n) * K * world / l_blocks[l_med], "ms_per_step": l_blocks[l_med] / K * 1e3,
-                      "launch_period_ms": sorted(l_periods)[len(l_periods) // 2], "blocks": len(l_blocks),
-                      "note": "the same K-launch blocks issued one by one from Python (one env.step_tensors call per launch) "
-                              "instead of one graph replay: what a caller's per-step loop pays at this block length"}
+        # ---- the same blocks with the actions drawn inside the launch (sf_step_sampled)
+        s_reps = 1 if args.timed_only else repeats
+        s_blocks, _, s_periods, s_ev = timed_blocks(graph_sampled, lambda t: step_sampled(), s_reps)
+        s_med, _ = pick(s_blocks, s_ev)
+        s_period = sorted(s_periods)[len(s_periods) // 2]
+        # ---- ... and, when the blocks above were HIP graphs, a few blocks issued one by one from Python: the per-call host path
+        loop_issue = None
+        if graph is not None and not args.timed_only:
+            l_blocks, _, l_periods, l_ev = timed_blocks(None, launch_ring, max(4, repeats // 8))
+            l_med, _ = pick(l_blocks, l_ev)
+            loop_issue = {"value": float(n) * K * world / l_blocks[l_med], "ms_per_step": l_blocks[l_med] / K * 1e3,
+                          "launch_period_ms": sorted(l_periods)[len(l_periods) // 2], "blocks": len(l_blocks),
+                          "note": "the same K-launch blocks issued one by one from Python (one env.step_tensors call per launch) "
+                                  "instead of one graph replay: what a caller's per-step loop pays at this block length"}
 
-    # ---- the launch period in steady state, outside the timed blocks: a short block starts on an idle GPU (first-launch
-    #      / graph-launch latency, packets barely ahead of the kernels), so its average reads above what the kernel
-    #      sustains.  Back-to-back launches from the Python loop for --steady-seconds, in chunks between HIP events: every
-    #      lane plays through whole episodes meanwhile (the statistics below are not zeros), and a utilisation sampler
-    #      outside this process gets to see the GPU busy.
-    chunk = 64 if args.timed_only else 4096
-    s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    step(act_rows[0])
-    sync()
-    n_steady, steady_total_ms, t_begin = 0, 0.0, time.perf_counter()
-    while n_steady < (chunk if args.timed_only else max(K, 2000)) or time.perf_counter() - t_begin < args.steady_seconds:
-        s0.record()
-        for t in range(chunk):
-            step(act_rows[t % ring])
-        s1.record()
+        # ---- the launch period in steady state, outside the timed blocks: a short block starts on an idle GPU (first-launch
+        #      / graph-launch latency, packets barely ahead of the kernels), so its average reads above what the kernel
+        #      sustains.  Back-to-back launches from the Python loop for --steady-seconds, in chunks between HIP events: every
+        #      lane plays through whole episodes meanwhile (the statistics below are not zeros), and a utilisation sampler
+        #      outside this process gets to see the GPU busy.
+        chunk = 64 if args.timed_only else 4096
+        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        step(act_rows[0])
         sync()
-        steady_total_ms += s0.elapsed_time(s1)
-        n_steady += chunk
-    steady_ms = steady_total_ms / n_steady
-    env.check_state()  # (raises on the sticky device error word: nothing below is reported for a batch that overflowed)
+        n_steady, steady_total_ms, t_begin = 0, 0.0, time.perf_counter()
+        while n_steady < (chunk if args.timed_only else max(K, 2000)) or time.perf_counter() - t_begin < args.steady_seconds:
+            s0.record()
+            for t in range(chunk):
+                step(act_rows[t % ring])
+            s1.record()
+            sync()
+            steady_total_ms += s0.elapsed_time(s1)
+            n_steady += chunk
+        steady_ms = steady_total_ms / n_steady
+        env.check_state()  # (raises on the sticky device error word: nothing below is reported for a batch that overflowed)
 
-    # ---- the only collective of the path, outside the timed blocks and timed on its own: 64 bytes over RCCL
-    sync()
-    ts = time.perf_counter()
-    stats = torch.from_numpy(env.episode_stats()).to(dev)  # D2H of 8 numbers: syncs this rank's stream
-    stats = reduce_episode_stats(stats, force=bool(force))
-    sync()
-    stats_reduce_us = (time.perf_counter() - ts) * 1e6
+        # ---- the only collective of the path, outside the timed blocks and timed on its own: 64 bytes over RCCL
+        sync()
+        ts = time.perf_counter()
+        stats = torch.from_numpy(env.episode_stats()).to(dev)  # D2H of 8 numbers: syncs this rank's stream
+        stats = reduce_episode_stats(stats, force=bool(force))
+        sync()
+        stats_reduce_us = (time.perf_counter() - ts) * 1e6
 
     # ---- who ran: one all-gather of (rank, device, PCI bus id, this rank's own median block)
     mine = dict(device_identity(torch, local_rank), rank=rank, lanes=[lane0, lane1], env_steps=(lane1 - lane0) * K,
@@ -562,19 +618,20 @@ def main():
             sys.stderr.write("bench.py: %d ranks on %d distinct devices (process group of %d): %r\n" % (world, len(set(ids)), rccl_world, ids))
             sys.exit(4)
 
-    # ---- each launch bracketed by its own event pair (the events themselves add about 2 us, so this reads high)
-    k = min(args.kernel_timing_launches, max(1, args.steps))
-    starts = [torch.cuda.Event(enable_timing=True) for _ in range(k)]
-    stops = [torch.cuda.Event(enable_timing=True) for _ in range(k)]
-    for t in range(k):
-        starts[t].record()
-        env.step_tensors(actions[t % ring])
-        stops[t].record()
-    torch.cuda.synchronize()
-    per = sorted(starts[t].elapsed_time(stops[t]) for t in range(k))
-    kern_ms = float(np.mean(per))
-    kern_ms_med = per[len(per) // 2]
-    env.check_actions()
+    if args.full:
+        # ---- each launch bracketed by its own event pair (the events themselves add about 2 us, so this reads high)
+        k = min(args.kernel_timing_launches, max(1, args.steps))
+        starts = [torch.cuda.Event(enable_timing=True) for _ in range(k)]
+        stops = [torch.cuda.Event(enable_timing=True) for _ in range(k)]
+        for t in range(k):
+            starts[t].record()
+            env.step_tensors(actions[t % ring])
+            stops[t].record()
+        torch.cuda.synchronize()
+        per = sorted(starts[t].elapsed_time(stops[t]) for t in range(k))
+        kern_ms = float(np.mean(per))
+        kern_ms_med = per[len(per) // 2]
+        env.check_actions()
     fused = None
     if args.rollout_k > 0:
         KF = min(args.rollout_k, ring)
@@ -601,7 +658,7 @@ def main():
                          "ticks resident up front, obs/reward/done/info written for every tick; bit-identical to K "
                          "sf_step launches (tests/test_gpu_parity.py::test_fused_rollout_equals_single_steps)"}
         del ro_out
-    solo = rank == 0 and world == 1  # the single-GPU extras: not part of an N > 1 run (its ranks would wait for rank 0)
+    solo = args.full and rank == 0 and world == 1  # the single-GPU extras: not part of an N > 1 run (its ranks would wait for rank 0)
     # a measured ceiling beside the 8 TB/s spec peak: device-to-device copy of 1 GiB, read + write bytes
     copy_gbs = None
     if solo:
@@ -770,12 +827,6 @@ def main():
         # time, MAX over ranks -- i.e. the sum of the ranks' shares at the job's clock (`ranks[*].value_share`)
         value = whole_job_value(ranks, elapsed)
         assert abs(value - total_steps / elapsed) <= 1e-9 * value, (value, total_steps / elapsed)
-        algo = ALGO_BYTES[args.gametype] * n
-        # `achieved` / `frac`: the algorithmic bytes of one launch over ms_per_step of the blocks that give `value` (the same
-        # clock as `value`); the HIP-event launch period of the event-carrying blocks stands beside it as a labelled extra
-        achieved = algo / (elapsed / K) / 1e9
-        achieved_event = algo / (region_ms * 1e-3) / 1e9
-        prof = committed_profile(args.gametype, n, args.obs_type)
         out = {
             "metric": METRIC,
             "value": value,
@@ -791,73 +842,82 @@ def main():
             "data": "synthetic",
             "repeats": repeats,
             "launch": "hip_graph (K sf_step launches captured once, one replay per block)" if use_graph else "loop (one Python call per launch)",
-            "loop_issue": loop_issue,
-            "block_ms": {"median": elapsed * 1e3, "min": blocks[order[0]] * 1e3, "max": blocks[order[-1]] * 1e3,
-                         "first": blocks[0] * 1e3, "blocks_without_events": len(order),
-                         "with_events_median": ev_blocks[len(ev_blocks) // 2] * 1e3 if ev_blocks else None,
-                         "blocks_with_events": len(ev_blocks),
-                         "note": "each block = exactly `steps` launches between barrier + synchronize brackets (max over "
-                                 "ranks).  Every other block also carries the pair of HIP events that measures "
-                                 "roofline.launch_period_ms; the two event packets cost such a block about 7 us of its own "
-                                 "(tools/block_probe.py), so value and ms_per_step come from the median of the blocks WITHOUT "
-                                 "them, and the event blocks' median stands beside it"},
-            "value_with_action_gen": total_steps / s_blocks[s_med],
-            "action_gen": {"value": total_steps / s_blocks[s_med], "unit": "env-steps/s", "ms_per_step": s_blocks[s_med] / K * 1e3,
-                           "launch_period_ms": s_period,
-                           "note": "the same timed blocks through sf_step_sampled: every lane draws its action inside the "
-                                   "launch (Philox4x32-10 keyed by seed, counter (lane of the job, tick); the tick counter "
-                                   "lives on the device, so every graph replay plays new actions); no action tensor is "
-                                   "generated, stored or loaded (SURVEY 8d: 'action generation on device ... report both'; "
-                                   "tests/test_gpu_sampled.py replays the sampled actions through the oracle)"},
-            "stats_reduce_us": stats_reduce_us,
             "config": {"workload": "%s, %d envs/GPU, %s obs (f32), uniform random discrete actions resident in HBM, "
                                    "per-lane auto-reset" % (args.gametype, n, args.obs_type),
                        "envs_per_gpu": n, "gametype": args.gametype, "obs_type": args.obs_type,
                        "parallelism": "%d contiguous lane shard(s) of one %d-lane batch, one process per GPU, no data-path "
                                       "collective" % (world, n * world)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "frac_source": "algorithmic_bytes_per_launch / ms_per_step (the blocks that give `value`)",
-                         "achieved_event_period": achieved_event, "frac_event_period": achieved_event / HBM_PEAK_GBS,
-                         "event_period_note": "the same bytes over launch_period_ms: HIP events around the launches of the "
-                                              "event-carrying blocks (end of the first launch to end of the last)",
-                         "frac_note": "of the 8 TB/s HBM spec peak; the 77 MB state of this workload is Infinity-Cache "
-                                      "resident (256 MB), so the bytes mostly move between L2 and the Infinity Cache",
-                         "measured_copy_ceiling_GBps": copy_gbs,
-                         "frac_of_copy_ceiling": (achieved / copy_gbs) if copy_gbs else None,
-                         "traffic": prof.get("traffic_bytes_per_launch"),
-                         "stale": prof.get("stale") if prof else None,
-                         "profile_build_id": prof.get("sf_build_id") if prof else None,
-                         "loaded_build_id": prof.get("loaded_build_id") if prof else None,
-                         "stale_note": "traffic and kernel_ms_rocprof are replayed from the committed rocprofv3 runs of the "
-                                       "build named in profile_build_id; stale = the loaded library is another build",
-                         "traffic_source": ("replayed from the committed rocprofv3 --pmc passes of kernel version %s "
-                                            "(profiles/%s), not measured by this run" % (prof.get("version"), prof.get("pmc_file")))
-                                           if prof else None,
-                         "kernel": "sf_step_kernel", "launch_period_ms": region_ms,
-                         "launch_period_steady_ms": steady_ms, "frac_steady": algo / (steady_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "steady_note": "%d back-to-back launches (%.1f s of the Python loop) outside the timed blocks; `achieved` / "
-                                        "`frac` use the timed blocks' ms_per_step, which for a block of a few launches includes its "
-                                        "start on an idle GPU" % (n_steady, steady_total_ms * 1e-3),
-                         "kernel_ms_rocprof": prof.get("kernel_ms_rocprof"),
-                         "kernel_ms_rocprof_median": prof.get("kernel_ms_rocprof_median"),
-                         "kernel_ms_rocprof_source": ("rocprofv3 --kernel-trace mean of kernel version %s (profiles/%s)"
-                                                      % (prof.get("version"), prof.get("trace_file"))) if prof else None,
-                         "kernel_ms_event_pair_mean": kern_ms, "kernel_ms_event_pair_median": kern_ms_med,
-                         "algorithmic_bytes_per_launch": algo, "launches_timed": K},
-            "cpu_baseline": base,
             "state_ok": state_ok,
             "state_ok_note": "env.check_state() (sf_check_state: the sticky device-side words -- a split launch's hand-over that timed "
                              "out, a per-episode counter or key timer that left its packed width) after the timed blocks, after the steady "
-                             "region and at the end: it raises on any error, so a line that prints has passed all three",
+                             "region (--full) and at the end: it raises on any error, so a line that prints has passed them all",
             "ranks": ranks,
             "rccl_world": rccl_world,
-            "rollout_fused": fused,
-            "host_api": host_api,
-            "image_obs": image_obs,
-            "configs": configs,
-            "episode_stats": summarize(stats.cpu()),
         }
+        if args.full:
+            algo = ALGO_BYTES[args.gametype] * n
+            # `achieved` / `frac`: the algorithmic bytes of one launch over ms_per_step of the blocks that give `value` (the same
+            # clock as `value`); the HIP-event launch period of the event-carrying blocks stands beside it as a labelled extra
+            achieved = algo / (elapsed / K) / 1e9
+            achieved_event = algo / (region_ms * 1e-3) / 1e9
+            prof = committed_profile(args.gametype, n, args.obs_type)
+            out.update({
+                "loop_issue": loop_issue,
+                "block_ms": {"median": elapsed * 1e3, "min": blocks[order[0]] * 1e3, "max": blocks[order[-1]] * 1e3,
+                             "first": blocks[0] * 1e3, "blocks_without_events": len(order),
+                             "with_events_median": ev_blocks[len(ev_blocks) // 2] * 1e3 if ev_blocks else None,
+                             "blocks_with_events": len(ev_blocks),
+                             "note": "each block = exactly `steps` launches between barrier + synchronize brackets (max over "
+                                     "ranks).  Every other block also carries the pair of HIP events that measures "
+                                     "roofline.launch_period_ms; the two event packets cost such a block about 7 us of its own "
+                                     "(tools/block_probe.py), so value and ms_per_step come from the median of the blocks WITHOUT "
+                                     "them, and the event blocks' median stands beside it"},
+                "value_with_action_gen": total_steps / s_blocks[s_med],
+                "action_gen": {"value": total_steps / s_blocks[s_med], "unit": "env-steps/s", "ms_per_step": s_blocks[s_med] / K * 1e3,
+                               "launch_period_ms": s_period,
+                               "note": "the same timed blocks through sf_step_sampled: every lane draws its action inside the "
+                                       "launch (Philox4x32-10 keyed by seed, counter (lane of the job, tick); the tick counter "
+                                       "lives on the device, so every graph replay plays new actions); no action tensor is "
+                                       "generated, stored or loaded (SURVEY 8d: 'action generation on device ... report both'; "
+                                       "tests/test_gpu_sampled.py replays the sampled actions through the oracle)"},
+                "stats_reduce_us": stats_reduce_us,
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS,
+                             "frac_source": "algorithmic_bytes_per_launch / ms_per_step (the blocks that give `value`)",
+                             "achieved_event_period": achieved_event, "frac_event_period": achieved_event / HBM_PEAK_GBS,
+                             "event_period_note": "the same bytes over launch_period_ms: HIP events around the launches of the "
+                                                  "event-carrying blocks (end of the first launch to end of the last)",
+                             "frac_note": "of the 8 TB/s HBM spec peak; the 77 MB state of this workload is Infinity-Cache "
+                                          "resident (256 MB), so the bytes mostly move between L2 and the Infinity Cache",
+                             "measured_copy_ceiling_GBps": copy_gbs,
+                             "frac_of_copy_ceiling": (achieved / copy_gbs) if copy_gbs else None,
+                             "traffic": prof.get("traffic_bytes_per_launch"),
+                             "stale": prof.get("stale") if prof else None,
+                             "profile_build_id": prof.get("sf_build_id") if prof else None,
+                             "loaded_build_id": prof.get("loaded_build_id") if prof else None,
+                             "stale_note": "traffic and kernel_ms_rocprof are replayed from the committed rocprofv3 runs of the "
+                                           "build named in profile_build_id; stale = the loaded library is another build",
+                             "traffic_source": ("replayed from the committed rocprofv3 --pmc passes of kernel version %s "
+                                                "(profiles/%s), not measured by this run" % (prof.get("version"), prof.get("pmc_file")))
+                                               if prof else None,
+                             "kernel": "sf_step_kernel", "launch_period_ms": region_ms,
+                             "launch_period_steady_ms": steady_ms, "frac_steady": algo / (steady_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "steady_note": "%d back-to-back launches (%.1f s of the Python loop) outside the timed blocks; `achieved` / "
+                                            "`frac` use the timed blocks' ms_per_step, which for a block of a few launches includes its "
+                                            "start on an idle GPU" % (n_steady, steady_total_ms * 1e-3),
+                             "kernel_ms_rocprof": prof.get("kernel_ms_rocprof"),
+                             "kernel_ms_rocprof_median": prof.get("kernel_ms_rocprof_median"),
+                             "kernel_ms_rocprof_source": ("rocprofv3 --kernel-trace mean of kernel version %s (profiles/%s)"
+                                                          % (prof.get("version"), prof.get("trace_file"))) if prof else None,
+                             "kernel_ms_event_pair_mean": kern_ms, "kernel_ms_event_pair_median": kern_ms_med,
+                             "algorithmic_bytes_per_launch": algo, "launches_timed": K},
+                "cpu_baseline": base,
+                "rollout_fused": fused,
+                "host_api": host_api,
+                "image_obs": image_obs,
+                "configs": configs,
+                "episode_stats": summarize(stats.cpu()),
+            })
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

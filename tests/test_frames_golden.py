@@ -4,6 +4,7 @@ tests/golden/frames/make_frames_golden.py and make_score_golden.py.  Bar: BIT-EX
 included (round 6: the text is a glyph atlas taken from the image's real cairo + FreeType and held to 2 520 frames of the
 reference's renderer: score_glyphs.npz, scores.npz).  No GPU; the HIP frames are held to the same fixtures in
 tests/test_gpu_image.py."""
+import hashlib
 import json
 import os
 
@@ -106,25 +107,38 @@ def test_model_equals_reference_frames_in_other_geometries():
     assert (R.W, R.H, R.SX, R.SY) == (90, 92, .2, .2)
 
 
+def live_renderer_ticks(g):
+    """The run of test_live_reference_renderer_if_built on `g` (a RefDrawGame or an OracleEnv, seed 7, spawn_skip 3): random
+    keys from a fixed stream; yields the ticks whose frame is compared (every 5th)."""
+    rng = np.random.default_rng(3)
+    keys = [0, 1, 2, 4, 8] if g.youturn else [0, 1, 2]
+    for t in range(1500):
+        g.apply_keys(int(rng.choice(keys)), g.youturn)
+        g.step_one_tick(34)
+        if t % 5 == 0:
+            yield t
+
+
 def test_live_reference_renderer_if_built(oracle_mod):
-    """Where oracle/_ref/libsfrefdraw.so exists (the build container): a fresh hunter run of the reference, every 5th
-    frame drawn by its renderer and by the model."""
+    """A fresh hunter run of the reference, every 5th frame drawn by its renderer and by the model: live where
+    oracle/_ref/libsfrefdraw.so exists (the build container); elsewhere the model draws the oracle's states of the same run
+    (bit-identical to the reference's: tests/test_oracle_golden.py) and is held to a digest of the reference's frames
+    (tests/golden/live_reference.json, written by tests/golden/make_live_golden.py)."""
     O = oracle_mod
-    if not O.have_refdraw():
-        pytest.skip("oracle/_ref/libsfrefdraw.so not built here (needs /root/reference + cairo)")
     from oracle import render_np as R
-    import sfscript
+    live = O.have_refdraw()
     for gt in ("youturn", "autoturn"):
-        g = O.RefDrawGame(gt, seed=7, spawn_skip=3)
+        g = O.RefDrawGame(gt, seed=7, spawn_skip=3) if live else O.OracleEnv(gt, seed=7, spawn_skip=3)
         hx = g.hex_points()
-        rng = np.random.default_rng(3)
-        keys = [0, 1, 2, 4, 8] if gt == "youturn" else [0, 1, 2]
-        for t in range(1500):
-            g.apply_keys(int(rng.choice(keys)), g.youturn)
-            g.step_one_tick(34)
-            if t % 5 == 0:
-                s = g.snapshot()
-                assert np.array_equal(R.render_raw(s, hx[:12], hx[12:]), g.draw()), (gt, t)
+        h = hashlib.sha256()
+        for t in live_renderer_ticks(g):
+            f = R.render_raw(g.snapshot(), hx[:12], hx[12:])
+            if live:
+                assert np.array_equal(f, g.draw()), (gt, t)
+            h.update(f.tobytes())
+        if not live:
+            with open(os.path.join(GOLDEN, "live_reference.json")) as fp:
+                assert h.hexdigest() == json.load(fp)["renderer"][gt], gt
 
 
 def test_model_equals_reference_frames_in_a_close_up():

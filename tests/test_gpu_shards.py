@@ -168,7 +168,7 @@ def _bench_rccl(extra):
     env = dict(os.environ, SF_BENCH_FORCE_DIST="nccl", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("SF_BENCH_CPU_BASELINE_FILE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--envs", "4096", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--envs", "4096", "--full", "--no-cpu-baseline",
                         "--rollout-k", "0", "--image-envs", "0", "--numpy-api", "0", "--no-configs", "--steady-seconds", "0.3",
                         "--kernel-timing-launches", "10"] + extra,
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
@@ -203,3 +203,26 @@ def test_the_drivers_scale_command_on_one_rank():
     assert rk["rank"] == 0 and rk["device_index"] == 0 and rk["lanes"] == [0, 4096] and rk["block_ms_median"] > 0
     assert rk["pci_bus_id"] is None or len(rk["pci_bus_id"]) >= 7
     assert j["episode_stats"]["episodes"] >= 4096  # the steady-state loop plays whole episodes: the all-gather carries counts
+
+
+def test_a_plain_bench_run_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: one timed block of exactly K launches, the headline
+    line alone, and what the last timed step returned (obs, reward, done, info) as float .npy files -- the same files from two
+    runs with the same arguments."""
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--envs", "4096", "--steps", "300",
+                            "--warmup", "20", "--dump-outputs", str(tmp_path / d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    for j in lines:
+        assert j["steps"] == 300 and j["repeats"] == 1 and j["launch"].startswith("hip_graph") and j["state_ok"]
+        assert j["value"] > 1e8 and abs(j["value"] * j["ms_per_step"] * 1e-3 - 4096) <= 1e-6 * 4096
+        assert not {"roofline", "cpu_baseline", "action_gen", "configs", "image_obs"} & set(j)
+    shapes = {"obs": (4096, 19), "reward": (4096,), "done": (4096,), "info": (4096,)}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in shapes)
+    for k, shape in shapes.items():
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and a.shape == shape and np.array_equal(a, b), k
+    assert np.isfinite(np.load(tmp_path / "a" / "obs.npy")).all()

@@ -1,9 +1,11 @@
 """The CPU oracle (oracle/sf_oracle.c) against the golden vectors generated
-from the real reference engine (tests/golden/make_golden.py), and -- where the
-reference build is present (build container) -- against the reference itself.
+from the real reference engine (tests/golden/make_golden.py), and against the
+reference itself: live where the reference build is present (build container),
+elsewhere as digests of the same runs (tests/golden/make_live_golden.py).
 
 Bar: every field bit-exact (the oracle makes the same libm calls on the same
 host libm as the reference did)."""
+import hashlib
 import json
 import os
 
@@ -188,25 +190,65 @@ def test_episode_length():
     assert np.flatnonzero(z["done"]).tolist() == [5294]  # 5295 steps per episode
 
 
-@pytest.mark.parametrize("gametype", ["youturn", "autoturn", "test-youturn", "test-autoturn"])
-def test_oracle_vs_reference_live(oracle_mod, gametype):
-    """Where oracle/_ref exists: lock-step random rollouts, every field bit-exact."""
-    O = oracle_mod
-    if not O.have_ref():
-        pytest.skip("oracle/_ref/libsfref.so not built here")
+def digest(snaps, *arrays):
+    """sha256 over every snapshot field (fields_differing's view of a snapshot: the fields' bytes, no padding) and the
+    arrays' values as int64 -- the form in which tests/golden/live_reference.json keeps runs of the real engine."""
+    h = hashlib.sha256()
+    for f in snaps.dtype.names:
+        h.update(np.ascontiguousarray(snaps[f]).tobytes())
+    for x in arrays:
+        h.update(np.asarray(x, np.int64).tobytes())
+    return h.hexdigest()
+
+
+def live_record(gametype):
+    """The live runs below as the real engine played them (tests/golden/make_live_golden.py): for a box without oracle/_ref."""
+    with open(os.path.join(GOLDEN, "live_reference.json")) as f:
+        return json.load(f)[gametype]
+
+
+def live_random_runs(O, gametype):
+    """test_oracle_vs_reference_live's lock-step random rollouts: (action set, OracleEnv, key table, actions), in order."""
     rng = np.random.default_rng(sum(map(ord, gametype)))
     for aset, T in ((1, 12000), (0, 6000)):
         o = O.OracleEnv(gametype, action_set=aset)
-        r = O.RefGame(gametype)
         keys = np.array(o.action_keys(), np.uint8)
-        acts = rng.integers(0, len(keys), T).astype(np.uint8)
+        yield aset, o, keys, rng.integers(0, len(keys), T).astype(np.uint8)
+
+
+def live_kill_runs(O, gametype, T=40000):
+    """test_oracle_vs_reference_live_kills' runs: (policy, OracleEnv, key table, actions), in order."""
+    rng = np.random.default_rng(1000 + sum(map(ord, gametype)))
+    for policy in ("hunter", "charger"):
+        o = O.OracleEnv(gametype, action_set=1)
+        keys = np.array(o.action_keys(), np.uint8)
+        if policy == "hunter":  # closed loop (nothing else aims the ship in a youturn game), played on a second oracle env
+            acts = aimed_hunter_actions(O.OracleEnv(gametype, action_set=1), T, rng)
+        else:
+            acts = open_loop_actions(policy, T, len(keys), rng, phase=int(rng.integers(0, 96)))
+        yield policy, o, keys, acts
+
+
+@pytest.mark.parametrize("gametype", ["youturn", "autoturn", "test-youturn", "test-autoturn"])
+def test_oracle_vs_reference_live(oracle_mod, gametype):
+    """Lock-step random rollouts, every field bit-exact: against the real engine where oracle/_ref exists, elsewhere against
+    the digests of the same runs of it (tests/golden/live_reference.json)."""
+    O = oracle_mod
+    rec = None if O.have_ref() else live_record(gametype)
+    shaped = gametype in ("youturn", "autoturn")
+    for aset, o, keys, acts in live_random_runs(O, gametype):
         oo = o.replay(acts)
-        rr = r.replay(keys[acts])
+        if rec is not None:
+            assert digest(oo["snaps"], oo["done"], oo["reward"]) == rec["random_aset%d" % aset], (gametype, aset)
+            continue
+        rr = O.RefGame(gametype).replay(keys[acts])
         assert not fields_differing(oo["snaps"], rr["snaps"]), (gametype, aset)
         assert np.array_equal(oo["done"], rr["done"])
-        shaped = gametype in ("youturn", "autoturn")
         assert np.array_equal(oo["reward"], shaped_reward(rr["eng_reward"], rr["snaps"]["vlner"], shaped))
     o = O.OracleEnv(gametype)
+    if rec is not None:
+        assert o.rollout(500000, 11) == rec["rollout"] and digest(o.snapshot()) == rec["rollout_snapshot"]
+        return
     r = O.RefGame(gametype)
     assert o.rollout(500000, 11) == r.rollout(500000, 11)
     assert o.snapshot().tobytes() == r.snapshot().tobytes()
@@ -216,35 +258,32 @@ def test_oracle_vs_reference_live(oracle_mod, gametype):
 def test_oracle_vs_reference_live_kills(oracle_mod, gametype):
     """The live check on the paths random play does not reach: the vlner state machine, destroy, the fortress's respawn,
     shell and hexagon deaths -- 40 000 hunter + 40 000 charger steps per preset (7.5 episodes each, new Game at game over)
-    through the REAL engine (oracle/_ref) and through the C restatement, every snapshot field of every tick bit-identical,
-    wrapper rewards (ENV:233-244) included."""
+    through the REAL engine (oracle/_ref; elsewhere the digests of the same runs of it, tests/golden/live_reference.json)
+    and through the C restatement, every snapshot field of every tick bit-identical, wrapper rewards (ENV:233-244) included."""
     O = oracle_mod
-    if not O.have_ref():
-        pytest.skip("oracle/_ref/libsfref.so not built here")
-    rng = np.random.default_rng(1000 + sum(map(ord, gametype)))
+    rec = None if O.have_ref() else live_record(gametype)
     shaped = gametype in ("youturn", "autoturn")
     T = 40000
-    for policy in ("hunter", "charger"):
-        o = O.OracleEnv(gametype, action_set=1)
-        r = O.RefGame(gametype)
-        keys = np.array(o.action_keys(), np.uint8)
-        if policy == "hunter":  # closed loop (nothing else aims the ship in a youturn game), played on a second oracle env
-            acts = aimed_hunter_actions(O.OracleEnv(gametype, action_set=1), T, rng)
-        else:
-            acts = open_loop_actions(policy, T, len(keys), rng, phase=int(rng.integers(0, 96)))
+    for policy, o, keys, acts in live_kill_runs(O, gametype, T):
         oo = o.replay(acts, want_obs=False, max_resets=16)
-        rr = r.replay(keys[acts])
-        assert not fields_differing(oo["snaps"], rr["snaps"]), (gametype, policy)
-        assert np.array_equal(oo["done"], rr["done"]) and oo["done"].sum() == T // 5295
-        assert np.array_equal(oo["reward"], shaped_reward(rr["eng_reward"], rr["snaps"]["vlner"], shaped))
-        st = rr["snaps"]["stats"]
-        ends = np.flatnonzero(rr["done"])
+        if rec is not None:
+            assert digest(oo["snaps"], oo["done"], oo["reward"]) == rec["kills_" + policy], (gametype, policy)
+            snaps, done, kills = oo["snaps"], oo["done"], rec["kills_%s_engine_rewards" % policy]
+        else:
+            rr = O.RefGame(gametype).replay(keys[acts])
+            assert not fields_differing(oo["snaps"], rr["snaps"]), (gametype, policy)
+            assert np.array_equal(oo["done"], rr["done"])
+            assert np.array_equal(oo["reward"], shaped_reward(rr["eng_reward"], rr["snaps"]["vlner"], shaped))
+            snaps, done, kills = rr["snaps"], rr["done"], int((np.asarray(rr["eng_reward"]) > 0).sum())
+        assert oo["done"].sum() == T // 5295
+        st = snaps["stats"]
+        ends = np.flatnonzero(done)
         # per-episode counters (a new Game zeroes them): summed over the finished episodes, plus the running one
         tot = st[ends].sum(axis=0) + st[-1]
         if policy == "hunter":
             # stats: 4 resets, 5 destroyed, 11 vlner increments, 12 max vlner (SRC/game.hh:29-43)
             assert tot[5] >= 20 and tot[4] >= 20 and tot[11] >= 400 and st[:, 12].max() >= 11, (gametype, tot)
-            assert oo["info"].sum() == (np.asarray(rr["eng_reward"]) > 0).sum() >= 20
+            assert oo["info"].sum() == kills >= 20
         else:
             # 0 big-hex, 1 small-hex, 2 shell deaths, 3 ship deaths (autoturn ships charge INTO the small hexagon)
             assert tot[0] + tot[1] >= 100 and tot[0] >= 1 and tot[1] >= 1 and tot[2] >= 1 and tot[3] == tot[:3].sum(), (gametype, tot)

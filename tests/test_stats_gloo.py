@@ -115,7 +115,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "SF_BENCH_CPU_BASELINE_FILE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                        "--cpu-seconds", "0.4", "--cpu-cores", "2"],
+                        "--full", "--cpu-seconds", "0.4", "--cpu-cores", "2"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -175,7 +175,7 @@ def test_world_of_eight_dry_run():
     import subprocess
 
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5",
-                        "--cpu-seconds", "0.3", "--cpu-cores", "2"],
+                        "--full", "--cpu-seconds", "0.3", "--cpu-cores", "2"],
                        env=_bench_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -225,3 +225,47 @@ def test_two_ranks_on_one_device_fail_the_job():
     assert r.returncode == 4, (r.returncode, r.stderr[-1000:])
     assert "distinct devices" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_a_plain_run_is_the_headline_alone():
+    """Without --full the line is the headline alone: one timed block of exactly --steps launches, no CPU baseline (the
+    gloo rehearsal of the control flow, as above)."""
+    import json
+    import subprocess
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+                       env=_bench_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 20 and j["repeats"] == 1 and j["cpu_baseline"] is None
+
+
+def test_dump_outputs_are_exact_floats_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: every array as float32 / float64 with its values unchanged; beyond the byte budget a seeded
+    sample of lanes, the same one for every array and from call to call, with its indices beside it."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n, names = 1000, ("obs", "reward", "done", "info")
+    g = torch.Generator().manual_seed(5)
+    outs = (torch.randn(n, 19, generator=g), torch.arange(n, dtype=torch.int32) - 500,
+            (torch.arange(n) % 3 == 0).to(torch.uint8), (torch.arange(n) % 7 == 0).to(torch.uint8))
+    bench.dump_outputs(str(tmp_path / "all"), outs, "", 1 << 30)
+    assert not (tmp_path / "all" / "lanes.npy").exists()
+    for k, t, dt in zip(names, outs, (np.float32, np.float64, np.float32, np.float32)):
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == dt and np.array_equal(a, t.numpy())
+    budget = 100 * (19 * 4 + 24)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs, "_rank1", budget)
+    lanes = np.load(tmp_path / "s1" / "lanes_rank1.npy")
+    assert lanes.dtype == np.float64 and len(lanes) == 100 and len(set(lanes)) == 100
+    assert np.array_equal(lanes, np.load(tmp_path / "s2" / "lanes_rank1.npy"))
+    total = lanes.nbytes
+    for k, t in zip(names, outs):
+        a = np.load(tmp_path / "s1" / (k + "_rank1.npy"))
+        assert np.array_equal(a, t.numpy()[lanes.astype(np.int64)])
+        total += a.nbytes
+    assert total <= budget
+    bench.dump_outputs(str(tmp_path / "f64"), (outs[0].double(),) + outs[1:], "", 1 << 30)
+    assert np.load(tmp_path / "f64" / "obs.npy").dtype == np.float64

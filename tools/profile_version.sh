@@ -15,7 +15,7 @@ OUT=$R/gpurun_out/profiles_${RND}_${VER}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 B="--steps 2000 --warmup 200 --no-cpu-baseline --numpy-api 0 --no-configs --steady-seconds 0.5"
-python3 $R/bench.py --steps 12000 --warmup 200 > $OUT/${RND}_bench_${VER}.json 2> $OUT/bench.err
+python3 $R/bench.py --full --steps 12000 --warmup 200 > $OUT/${RND}_bench_${VER}.json 2> $OUT/bench.err
 echo "bench done"
 # the traced run launches its timed blocks as HIP graphs (512 launches per replay): launched one by one under the profiler the
 # kernels are no longer back to back (its per-dispatch work is on the host) and every one starts on an idle chip
