@@ -15,8 +15,9 @@
  *     `stream` is a hipStream_t passed as void* (NULL = the default stream).
  *   - every *_dev pointer is DEVICE memory owned by the caller (PyTorch); the
  *     library borrows it for the duration of the stream work it enqueues and
- *     makes no allocation after sf_create (one exception: the first image frame
- *     of a batch allocates that batch's render caches).
+ *     makes no allocation after sf_create (two exceptions: the first image frame
+ *     of a batch allocates that batch's render caches; sf_render_view the tables
+ *     of a view it has not drawn lately).
  *   - calls are asynchronous and stream-ordered; nothing synchronises unless
  *     documented (sf_get_field / sf_episode_stats do).
  *   - every function returns an sf_status (0 = ok, < 0 = error);
@@ -218,6 +219,44 @@ int sf_set_score_glyphs(sf_batch* b, const sf_score_glyphs* layout, const uint8_
 int sf_get_score_glyphs(const sf_batch* b, int32_t* has_atlas, sf_score_glyphs* layout, uint8_t* alpha, size_t alpha_bytes);
 /* the built-in atlas of the default geometry (host only, no GPU needed): alpha uint8[11][4][4] */
 int sf_default_score_glyphs(sf_score_glyphs* layout, uint8_t* alpha, size_t alpha_bytes);
+
+/* ---- Frames in a VIEW: what the reference's Game(config, lw, grayscale, width, height, viewport).draw() leaves in
+ *      pb_pixels (SRC/pymodule.cpp:319-354, SRC/draw.cpp:227-270), for lanes of any batch, grey or colour, at up to 1.0 pixel
+ *      per user unit -- a frame a person can watch (the human-play front-end's view is 450 x 460 in colour).
+ *        width, height     the surface; -1: the viewport's size
+ *        vp_x .. vp_h      the viewport; vp_w / vp_h -1: the config's 710 x 626 (vp_x, vp_y stay as given)
+ *        line_width        user units (the reference's default: 2)
+ *        grayscale         0: colour (the reference's default), 1: grey
+ *        format            SF_VIEW_BGRX: H x W x 4 bytes B, G, R, 255 (pb_pixels); SF_VIEW_RGB: H x W x 3 (R, G, B: video tools,
+ *                          gym's rgb_array); SF_VIEW_GRAY: H x W (grey views only)
+ *        glyphs, glyph_alpha  the score text's atlas for this view (sf_score_glyphs, 11 gw gh bytes); NULL: the built-in atlas
+ *                          of 1.0 pixel per unit where the viewport's offset is whole, else the seven-segment fallback
+ *      Limits (SF_ERR_ARG with a message): more than 1.0 pixel per unit either way, a side over 1024 pixels, a non-positive
+ *      viewport or line width, SF_VIEW_GRAY in colour.
+ *      sf_view_size resolves the defaults against the batch's config into *width, *height: the frame sf_render_view writes.
+ *      sf_view_check does the same against the 710 x 626 playfield every config has (host only, no GPU, no batch).
+ *      sf_render_view draws lanes
+ *      [first_lane, first_lane + n_lanes) into out_dev, lane k's frame at k * lane_stride bytes (0: the frame's size); it
+ *      reads the state only -- no state, RNG, cache or statistic changes -- and is ordered on `stream` (NULL: the batch's).
+ *      sf_view_circle_segments: how many Bezier segments cairo cuts half of the explosion's radius-7 circle into under the
+ *      matrix (xx, yx, xy, yy) (cairo-arc.c: _arc_segments_needed, tolerance 0.1): 1 up to 5.4 device pixels, then 2. ---- */
+#define SF_VIEW_BGRX 0
+#define SF_VIEW_RGB 1
+#define SF_VIEW_GRAY 2
+typedef struct sf_view {
+  int32_t width, height;
+  double vp_x, vp_y, vp_w, vp_h;
+  double line_width;
+  int32_t grayscale;
+  int32_t format;
+  const sf_score_glyphs* glyphs;
+  const uint8_t* glyph_alpha;
+} sf_view;
+int sf_view_check(const sf_view* view, int32_t* width, int32_t* height);
+int sf_view_size(const sf_batch* b, const sf_view* view, int32_t* width, int32_t* height);
+int sf_render_view(sf_batch* b, const sf_view* view, int first_lane, int n_lanes, uint8_t* out_dev, size_t lane_stride,
+                   void* stream);
+int sf_view_circle_segments(double xx, double yx, double xy, double yy, double radius);
 
 /* One step of the trainer's frame stack in one launch (rl/train.py:51-56,92-97): the 84x84 frame of every env
  * goes to slot `slot` of stack_dev uint8 [n_envs][num_stack][84][84] (16-byte aligned), and an env whose

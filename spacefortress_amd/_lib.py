@@ -65,6 +65,16 @@ class ScoreGlyphs(C.Structure):
     _fields_ = [("gw", C.c_int32), ("gh", C.c_int32), ("advance", C.c_int32), ("y0", C.c_int32), ("x0", (C.c_int16 * 10) * 11)]
 
 
+VIEW_FORMATS = {"bgrx": 0, "rgb": 1, "gray": 2}  # SF_VIEW_* (include/sfmi.h)
+
+
+class View(C.Structure):
+    """sf_view (include/sfmi.h): a view of sf_render_view"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("vp_x", C.c_double), ("vp_y", C.c_double), ("vp_w", C.c_double),
+                ("vp_h", C.c_double), ("line_width", C.c_double), ("grayscale", C.c_int32), ("format", C.c_int32),
+                ("glyphs", C.POINTER(ScoreGlyphs)), ("glyph_alpha", C.c_void_p)]
+
+
 # every symbol include/sfmi.h declares: (restype, argtypes)
 SYMBOLS = {
     "sf_create": (C.c_int, [C.POINTER(CreateParams), C.POINTER(C.c_void_p)]),
@@ -98,6 +108,10 @@ SYMBOLS = {
     "sf_set_score_glyphs": (C.c_int, [C.c_void_p, C.POINTER(ScoreGlyphs), C.c_void_p]),
     "sf_get_score_glyphs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(ScoreGlyphs), C.c_void_p, C.c_size_t]),
     "sf_default_score_glyphs": (C.c_int, [C.POINTER(ScoreGlyphs), C.c_void_p, C.c_size_t]),
+    "sf_view_check": (C.c_int, [C.POINTER(View), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sf_view_size": (C.c_int, [C.c_void_p, C.POINTER(View), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sf_render_view": (C.c_int, [C.c_void_p, C.POINTER(View), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sf_view_circle_segments": (C.c_int, [C.c_double] * 5),
     "sf_preset_get": (C.c_int, [C.c_char_p, C.POINTER(Preset)]),
     "sf_action_table": (C.c_int, [C.c_char_p, C.c_int, C.c_void_p]),
     "sf_spawn_table": (C.c_int, [C.c_uint32, C.c_int, C.c_void_p]),

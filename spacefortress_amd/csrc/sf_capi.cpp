@@ -12,6 +12,7 @@
 #include "sf_drawrec.h"
 #include "sf_internal.h"
 #include "sf_raster.h"
+#include "sf_view.h"
 
 struct sf_batch {
   SfKernelArgs args;
@@ -59,6 +60,20 @@ struct sf_batch {
   // and the atlas the default geometry's static backgrounds and cached pictures were made with
   SfGlyphAtlas h_glyphs, baked_glyphs;
   SfGlyphAtlas* d_glyphs;
+  // sf_render_view: the device tables of the views drawn last (sf_view_host.cpp), kViewCache of them, least recently used
+  // out first: a caller that alternates between a few views (a recorder's colour view and an agent's grey one) makes each once
+  struct ViewCache* views;
+  unsigned long long view_clock;
+};
+
+constexpr int kViewCache = 4;
+struct ViewCache {
+  SfViewRes res;  // (its planes and format aside: the tables do not depend on them)
+  uint8_t* d_bg;
+  size_t bg_stride;
+  double* d_circle;
+  SfGlyphAtlas* d_glyphs;
+  unsigned long long used;  // 0: an empty entry
 };
 
 namespace {
@@ -458,6 +473,14 @@ extern "C" int sf_destroy(sf_batch* b) {
   if (b->d_gbg) (void)hipFree(b->d_gbg);
   if (b->d_gtabs) (void)hipFree(b->d_gtabs);
   if (b->d_glyphs) (void)hipFree(b->d_glyphs);
+  if (b->views) {
+    for (int i = 0; i < kViewCache; i++) {
+      if (b->views[i].d_bg) (void)hipFree(b->views[i].d_bg);
+      if (b->views[i].d_circle) (void)hipFree(b->views[i].d_circle);
+      if (b->views[i].d_glyphs) (void)hipFree(b->views[i].d_glyphs);
+    }
+    delete[] b->views;
+  }
   if (b->args.dbg) (void)hipFree(b->args.dbg);
   if (b->args.hint) (void)hipFree(b->args.hint);
   delete b;
@@ -1184,5 +1207,100 @@ extern "C" int sf_get_field_dev(sf_batch* b, int f, void* dev, size_t bytes, voi
   DeviceGuard guard(b->device);
   SF_FLUSH_VIEW(b, (hipStream_t)stream);
   HIP_TRY(sf_launch_field_copy(b->d_state, b->n_envs, f, (unsigned char*)dev, 1, (hipStream_t)stream));
+  return SF_OK;
+}
+
+// ---- sf_render_view (sf_render_view.hip): frames in a view, for a range of lanes, from the state --------------------------------
+namespace {
+bool same_tables(const SfViewRes& a, const SfViewRes& b) {
+  return a.w == b.w && a.h == b.h && a.sx == b.sx && a.sy == b.sy && a.vx == b.vx && a.vy == b.vy && a.lw == b.lw && a.band_h == b.band_h &&
+         a.circle_k == b.circle_k && memcmp(&a.glyphs, &b.glyphs, sizeof(SfGlyphAtlas)) == 0;
+}
+}  // namespace
+
+// the batch's tables of view r: a cache entry, made on a miss (synchronous; an evicted entry's tables are freed only after the
+// device has finished every frame that may read them)
+static int view_tables(sf_batch* b, const SfViewRes& r, const ViewCache** out) {
+  if (!b->views) b->views = new ViewCache[kViewCache]();
+  int pick = 0;
+  for (int i = 0; i < kViewCache; i++) {
+    ViewCache& v = b->views[i];
+    if (v.used && same_tables(v.res, r)) {
+      v.used = ++b->view_clock;
+      *out = &v;
+      return SF_OK;
+    }
+    if (v.used < b->views[pick].used) pick = i;
+  }
+  std::vector<uint8_t> bg;
+  std::vector<double> circle;
+  size_t bg_stride = 0;
+  const int rc = sf_view_tables(r, &bg, &bg_stride, &circle);
+  if (rc != SF_OK) return rc;
+  ViewCache& v = b->views[pick];
+  if (v.used) {
+    HIP_TRY(hipDeviceSynchronize());  // (frames of the evicted view may still read its tables)
+    (void)hipFree(v.d_bg);
+    (void)hipFree(v.d_circle);
+    v.d_bg = nullptr;
+    v.d_circle = nullptr;
+    v.used = 0;
+  }
+  HIP_TRY(hipMalloc((void**)&v.d_bg, bg.size()));
+  HIP_TRY(hipMalloc((void**)&v.d_circle, circle.size() * sizeof(double)));
+  if (!v.d_glyphs) HIP_TRY(hipMalloc((void**)&v.d_glyphs, sizeof(SfGlyphAtlas)));
+  HIP_TRY(hipMemcpy(v.d_bg, bg.data(), bg.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(v.d_circle, circle.data(), circle.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(v.d_glyphs, &r.glyphs, sizeof(SfGlyphAtlas), hipMemcpyHostToDevice));
+  v.res = r;
+  v.bg_stride = bg_stride;
+  v.used = ++b->view_clock;
+  *out = &v;
+  return SF_OK;
+}
+
+extern "C" int sf_view_size(const sf_batch* b, const sf_view* view, int32_t* width, int32_t* height) {
+  if (!b) {
+    sf_set_error("sf_view_size: null batch");
+    return SF_ERR_ARG;
+  }
+  SfViewRes r;
+  const int rc = sf_view_resolve(view, b->preset.width, b->preset.height, &r);
+  if (rc != SF_OK) return rc;
+  if (width) *width = r.w;
+  if (height) *height = r.h;
+  return SF_OK;
+}
+
+extern "C" int sf_render_view(sf_batch* b, const sf_view* view, int first_lane, int n_lanes, uint8_t* out_dev, size_t lane_stride,
+                              void* stream) {
+  if (!b) {
+    sf_set_error("sf_render_view: null batch");
+    return SF_ERR_ARG;
+  }
+  SfViewRes r;
+  int rc = sf_view_resolve(view, b->preset.width, b->preset.height, &r);
+  if (rc != SF_OK) return rc;
+  if (first_lane < 0 || n_lanes < 0 || (long)first_lane + n_lanes > (long)b->n_envs) {
+    sf_set_error("sf_render_view: lanes [%d, %d + %d) are not inside the batch's %d", first_lane, first_lane, n_lanes, b->n_envs);
+    return SF_ERR_ARG;
+  }
+  const size_t frame = (size_t)r.w * r.h * (r.format == SF_VIEW_GRAY ? 1 : (r.format == SF_VIEW_RGB ? 3 : 4));
+  if (lane_stride == 0) lane_stride = frame;
+  if (!out_dev || lane_stride < frame) {
+    sf_set_error("sf_render_view: need an output and a lane stride of at least the frame's %zu bytes", frame);
+    return SF_ERR_ARG;
+  }
+  if (n_lanes == 0) return SF_OK;
+  DeviceGuard guard(b->device);
+  const ViewCache* tables = nullptr;
+  rc = view_tables(b, r, &tables);
+  if (rc != SF_OK) return rc;
+  SF_FLUSH_VIEW(b, stream);
+  const ViewCache& v = *tables;
+  const SfViewLaunch L{b->d_state, first_lane, n_lanes, r.w, r.h, r.band_h, r.planes, r.format, r.sx, r.sy, r.vx, r.vy, r.lw,
+                       b->d_consts + SF_LDS_TRIG, b->d_arcs, v.d_circle, r.circle_k, v.d_bg, v.bg_stride, v.d_glyphs, out_dev,
+                       lane_stride};
+  HIP_TRY(sf_launch_render_view(L, (hipStream_t)stream));
   return SF_OK;
 }

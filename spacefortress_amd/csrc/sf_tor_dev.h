@@ -129,13 +129,53 @@ __device__ __forceinline__ int slot_of(int okind, int k, int nq, int m0) {
   return okind == kKindRing ? (k == 0 ? 0 : (k == m0 - 1 ? 1 : (k == m0 ? 2 : (k == nq - 1 ? 3 : -1)))) : (k < 4 ? k : -1);
 }
 
+// ---- the BAND form (sf_render_view.hip, raster<M, true>): a workgroup draws pixel rows [r0, r1) of a surface up to 1024 pixels
+// wide, into planes that hold only those rows, grey or B, G, R.  Only the objects' boxes change (clipped to the band, their
+// fields wider, their rows counted from r0) and the circle's seams: cairo cuts a circle of more than 5.4 device pixels into
+// FOUR Bezier segments (cairo-arc.c), so the stroke has four seams where consecutive curves' pieces overlap, not two.
+struct Band {
+  int r0, r1;      // the band's rows; row r0 is the planes' row 0
+  int planes;      // 1: grey (the object's grey); 3: planes B, G, R, pstride bytes apart, each lerped to its byte of rgb
+  int pstride;
+  unsigned rgb;    // B | G << 8 | R << 16: the call's source values (planes == 3)
+  unsigned seams;  // a circle's curves: K | first piece of curve 1 << 8 | of curve 2 << 14 | of curve 3 << 20 (K = 2 or 4)
+};
+// a box in one word: x0 (10 bits) | w (11) | rows from the band's top (5) | h (6)
+__device__ __forceinline__ uint32_t band_box(int x0, int yr, int w, int h) {
+  return (uint32_t)x0 | ((uint32_t)w << 10) | ((uint32_t)yr << 21) | ((uint32_t)h << 26);
+}
+// the slots of piece k of a circle of K curves (bit 2c: the first piece of curve c, bit 2c + 1: its last), else the quad's own
+// slot below 4 as in slot_of
+__device__ __forceinline__ unsigned band_slots(int okind, int k, int nq, unsigned seams) {
+  if (okind != kKindRing) return k < 4 ? 1u << k : 0u;
+  const int K = (int)(seams & 7u);
+  unsigned m = 0u;
+  for (int c = 0; c < K; c++) {
+    const int st = c == 0 ? 0 : (int)((seams >> (8 + 6 * (c - 1))) & 63u);
+    const int en = c == K - 1 ? nq : (int)((seams >> (8 + 6 * c)) & 63u);
+    m |= (k == st ? 1u << (2 * c) : 0u) | (k == en - 1 ? 2u << (2 * c) : 0u);
+  }
+  return m;
+}
+// multi_sources over eight slots, a byte per set: a circle's seams {last of curve c, first of curve c + 1 mod K}
+__device__ __forceinline__ unsigned band_sources(int okind, unsigned seams) {
+  if ((okind & 255) != kKindRing) {
+    const unsigned n = multi_sources(okind);
+    return (n & 15u) | ((n >> 4) & 15u) << 8 | ((n >> 8) & 15u) << 16 | ((n >> 12) & 15u) << 24;
+  }
+  const int K = (int)(seams & 7u);
+  unsigned m = 0u;
+  for (int c = 0; c < K; c++) m |= ((2u << (2 * c)) | (1u << (2 * ((c + 1) % K)))) << (8 * c);
+  return m;
+}
+
 // MAXACT: how many quads of one object a pixel row taken whole may hold (4: lines; 8: a circle at a large scale -- more and the
 // row is sampled in sub-rows instead, which cairo does not do: the general kernel's circles stay below)
 #ifndef SFTD_STOP
 #define SFTD_STOP 9 /* diagnostic builds: leave raster() behind phase N (0: at once, 1 records + boxes, 2 rows, 3 sub-rows) */
 #endif
-template <int MAXACT = 4>
-__device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool valid, int obj0, int kind, int grey) {
+template <int MAXACT = 4, bool kBand = false>
+__device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool valid, int obj0, int kind, int grey, const Band& band = Band{}) {
   if (SFTD_STOP == 0) return;
   const int lane = C.lane, XM = C.W * 256;
   uint32_t* const acc = C.acc();
@@ -191,7 +231,7 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
     uint32_t* o = C.obj(lane);
     const int* oi_ = reinterpret_cast<const int*>(o);
     const int x0 = max(oi_[0] >> 8, 0), x1 = min((oi_[2] + 255) >> 8, C.W);
-    const int s0 = max(oi_[1], 0), s1 = min(oi_[3], C.H * sft::kGridY);
+    const int s0 = max(oi_[1], kBand ? band.r0 * sft::kGridY : 0), s1 = min(oi_[3], (kBand ? band.r1 : C.H) * sft::kGridY);
     if (x1 > x0 && s1 > s0) { fx0 = x0; fw = x1 - x0; fs0 = s0; fs1 = s1; }
     m0_mine = (int)o[7];
     o[4] |= o[5] << 8;  // (the object's quads, counted above)
@@ -227,7 +267,8 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
   const int tot_pix = __builtin_amdgcn_readlane(abase, kMaxObjs - 1);
   if (lane < nobj) {
     uint32_t* o = C.obj(lane);
-    o[0] = (uint32_t)bx0 | ((uint32_t)by0 << 8) | ((uint32_t)bw << 16) | ((uint32_t)bh << 24);
+    if constexpr (kBand) o[0] = band_box(bx0, bw > 0 ? by0 - band.r0 : 0, bw, bh);
+    else o[0] = (uint32_t)bx0 | ((uint32_t)by0 << 8) | ((uint32_t)bw << 16) | ((uint32_t)bh << 24);
     o[1] = (uint32_t)S0 | ((uint32_t)m0_mine << 16);    // (+ a circle's first half in the upper bits)
     o[2] = (uint32_t)nsub;
     o[3] = (uint32_t)(abase - bw * bh);         // where the object's accumulator starts (pixels)
@@ -249,7 +290,9 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
     if (t >= tot_rows) continue;
     const int o = find_obj(t, 5);
     const uint32_t* ob = C.obj(o);
-    const int obx0 = (int)(ob[0] & 255u), oby0 = (int)((ob[0] >> 8) & 255u), obw = (int)((ob[0] >> 16) & 255u);
+    int obx0, oby0, obw;
+    if constexpr (kBand) { obx0 = (int)(ob[0] & 1023u); obw = (int)((ob[0] >> 10) & 2047u); oby0 = band.r0 + (int)((ob[0] >> 21) & 31u); }
+    else { obx0 = (int)(ob[0] & 255u); oby0 = (int)((ob[0] >> 8) & 255u); obw = (int)((ob[0] >> 16) & 255u); }
     const int q0 = (int)(ob[4] & 255u), nq = (int)((ob[4] >> 8) & 255u), okind = (int)((ob[4] >> 16) & 255u);
     const int r = t - (int)ob[5], row = oby0 + r, s0 = row * sft::kGridY, m0 = (int)(ob[1] >> 16);
     bool full = true;
@@ -337,13 +380,13 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
     if (full && nact_q > 0) {
       __hip_atomic_fetch_or(const_cast<uint32_t*>(ob) + 6, 1u << r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       // every source with all its members in the row: left = the member edge last in the list, right = the first
-      const unsigned multi = multi_sources(okind);
+      const unsigned multi = kBand ? band_sources(okind, band.seams) : multi_sources(okind);
       const int arow = (int)ob[3] + r * obw;
       for (int si = 0; si < nact_q + 4; si++) {  // every quad in the row alone, then the object's overlap sets
         unsigned members = 0u;
         int sign = 1;
         if (si >= nact_q) {
-          members = (multi >> (4 * (si - nact_q))) & 15u;
+          members = kBand ? (multi >> (8 * (si - nact_q))) & 255u : (multi >> (4 * (si - nact_q))) & 15u;
           if (!members) continue;
           sign = (__popc(members) & 1) ? 1 : -1;
         }
@@ -351,8 +394,12 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
         for (int a = 0; a < nact_q; a++) {
           if (si < nact_q) { if (a != si) continue; }
           else {
-            const int sl = slot_of(okind, a_quad[a], nq, m0);
-            if (sl < 0 || !((members >> sl) & 1u)) continue;
+            if constexpr (kBand) {
+              if (!(band_slots(okind, a_quad[a], nq, band.seams) & members)) continue;
+            } else {
+              const int sl = slot_of(okind, a_quad[a], nq, m0);
+              if (sl < 0 || !((members >> sl) & 1u)) continue;
+            }
           }
           cnt++;
           if (lq < 0 || a_lt[a] > lt || (a_lt[a] == lt && a_lb[a] > lb)) { lq = a_quad[a]; lt = a_lt[a]; lb = a_lb[a]; le = a_le[a]; }
@@ -387,31 +434,41 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
     if (t >= tot_sub) continue;
     const int o = find_obj(t, 7);
     const uint32_t* ob = C.obj(o);
-    const int obx0 = (int)(ob[0] & 255u), oby0 = (int)((ob[0] >> 8) & 255u), obw = (int)((ob[0] >> 16) & 255u);
+    int obx0, oby0, obw;
+    if constexpr (kBand) { obx0 = (int)(ob[0] & 1023u); obw = (int)((ob[0] >> 10) & 2047u); oby0 = band.r0 + (int)((ob[0] >> 21) & 31u); }
+    else { obx0 = (int)(ob[0] & 255u); oby0 = (int)((ob[0] >> 8) & 255u); obw = (int)((ob[0] >> 16) & 255u); }
     const int q0 = (int)(ob[4] & 255u), nq = (int)((ob[4] >> 8) & 255u), okind = (int)((ob[4] >> 16) & 255u);
     const int s = (int)(ob[1] & 0xffffu) + t - (int)ob[7], m0 = (int)(ob[1] >> 16);
     const int row = s / sft::kGridY, r = row - oby0;
     if ((ob[6] >> r) & 1u) continue;  // taken whole
     const int arow = (int)ob[3] + r * obw;
-    int sl[4] = {0, 0, 0, 0}, sr[4] = {0, 0, 0, 0};  // the spans kept for the overlaps (slots 0..3)
+    constexpr int NS = kBand ? 8 : 4;
+    int sl[NS] = {}, sr[NS] = {};  // the spans kept for the overlaps (slots 0..3; the band form's circle: 0..7)
     for (int k = 0; k < nq; k++) {
       const RecView rv{C.rec(q0 + k)};
       int L = 0, R = 0;
       if (s >= rv.s0() && s < rv.s1()) rec_interval(rv, s, XM, &L, &R);
       add_span(acc, arow, obx0, obw, L, R, 1);
-      const int slot = slot_of(okind, k, nq, m0);
+      if constexpr (kBand) {
+        const unsigned sm = band_slots(okind, k, nq, band.seams);
 #pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (slot == j) { sl[j] = L; sr[j] = R; }
+        for (int j = 0; j < NS; j++)
+          if ((sm >> j) & 1u) { sl[j] = L; sr[j] = R; }
+      } else {
+        const int slot = slot_of(okind, k, nq, m0);
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          if (slot == j) { sl[j] = L; sr[j] = R; }
+      }
     }
-    const unsigned multi = multi_sources(okind);
+    const unsigned multi = kBand ? band_sources(okind, band.seams) : multi_sources(okind);
 #pragma unroll
     for (int si = 0; si < 4; si++) {
-      const unsigned members = (multi >> (4 * si)) & 15u;
+      const unsigned members = kBand ? (multi >> (8 * si)) & 255u : (multi >> (4 * si)) & 15u;
       if (!members) continue;
       int L = sft::kCellMin, R = sft::kCellMax;
 #pragma unroll
-      for (int j = 0; j < 4; j++)
+      for (int j = 0; j < NS; j++)
         if ((members >> j) & 1u) {
           // (an inactive or empty member has R <= L: the intersection is empty)
           if (sr[j] <= sl[j]) { L = 1; R = 0; }
@@ -426,7 +483,9 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
   // ---- pixels: object after object (the reference composites its strokes in order; boxes of different objects may overlap)
   for (int o = 0; o < nobj; o++) {
     const uint32_t* ob = C.obj(o);
-    const int obx0 = (int)(ob[0] & 255u), oby0 = (int)((ob[0] >> 8) & 255u), obw = (int)((ob[0] >> 16) & 255u), obh = (int)(ob[0] >> 24);
+    int obx0, oby0, obw, obh;  // (the band form: oby0 counts from the band's top, the planes' row 0)
+    if constexpr (kBand) { obx0 = (int)(ob[0] & 1023u); obw = (int)((ob[0] >> 10) & 2047u); oby0 = (int)((ob[0] >> 21) & 31u); obh = (int)(ob[0] >> 26); }
+    else { obx0 = (int)(ob[0] & 255u); oby0 = (int)((ob[0] >> 8) & 255u); obw = (int)((ob[0] >> 16) & 255u); obh = (int)(ob[0] >> 24); }
     const int ab = (int)ob[3], ogrey = (int)(ob[4] >> 24), n = obw * obh;
     for (int i = lane; i < n; i += 64) {
       const int ry = i / obw, rx = i - ry * obw;
@@ -434,7 +493,13 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
       const int a = sft::area_to_alpha(cov);
       if (a) {
         uint8_t* p = C.fb + (oby0 + ry) * C.W + obx0 + rx;
-        *p = (uint8_t)sft::lerp8(ogrey, a, *p);
+        if constexpr (kBand) {
+          if (band.planes == 1) *p = (uint8_t)sft::lerp8(ogrey, a, *p);
+          else
+            for (int c = 0; c < 3; c++) p[c * band.pstride] = (uint8_t)sft::lerp8((int)((band.rgb >> (8 * c)) & 255u), a, p[c * band.pstride]);
+        } else {
+          *p = (uint8_t)sft::lerp8(ogrey, a, *p);
+        }
       }
     }
     C.sync();

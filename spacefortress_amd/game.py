@@ -50,10 +50,16 @@ class Game:
         self.shot_intervals_invul, self.shot_intervals_vul = (), ()
         self._obs = None
         self._sd = None
-        self.pb_width, self.pb_height = (width, height) if width > 0 else (90, 92)
         p = _lib.Preset()
         _lib.check(_lib.lib().sf_preset_get(config.encode(), C.byref(p)))
         self._preset = p
+        # the pixel buffer's view with the reference's defaulting (SRC/pymodule.cpp:345-351): viewport size -1 -> the config's,
+        # surface -1 -> the viewport's; draw() renders this lane in it (sf_render_view), checked there
+        vx, vy, vw, vh = (int(v) for v in viewport)
+        vw, vh = p.width if vw == -1 else vw, p.height if vh == -1 else vh
+        width, height = vw if width == -1 else int(width), vh if height == -1 else int(height)
+        self._view = dict(width=width, height=height, viewport=(vx, vy, vw, vh), lw=float(lw), grayscale=bool(grayscale))
+        self.pb_width, self.pb_height = width, height
         self._owns = True
 
     @classmethod
@@ -83,6 +89,7 @@ class Game:
         g._obs = None
         g._sd = None
         g.pb_width, g.pb_height = width, height
+        g._view = None  # (the env's own geometry: its batch's frames)
         p = _lib.Preset()
         _lib.check(_lib.lib().sf_preset_get(config.encode(), C.byref(p)))
         g._preset = p
@@ -173,17 +180,26 @@ class Game:
     def is_game_over(self):
         return bool(self.time >= self.max_time)
 
+    # SSF_Env's view (ENV:164): the batch's own image geometry, whose frames its frame kernel draws
+    _SSF_VIEW = dict(width=90, height=92, viewport=(130, 80, 450, 460), lw=3.0, grayscale=True)
+
     def draw(self):
-        self._frame = self._vec.render("image-raw")[0].cpu().numpy()
+        v = self._view
+        if v is None or v == self._SSF_VIEW:
+            self._frame = self._vec.render("image-raw")[0].cpu().numpy()
+        else:
+            self._frame = self._vec.render_view(**v, format="bgrx", lanes=0)[0].cpu().numpy()
 
     @property
     def pb_pixels(self):
-        """The surface as the reference exposes it: rows of 4 bytes per pixel (B, G, R, x); the grey value three times and
-        255 -- what cairo's ARGB32 surface holds there behind an opaque paint (tests/golden/getters: `frames`)."""
+        """The surface as the reference exposes it: rows of 4 bytes per pixel (B, G, R, x) -- in grey the grey value three times
+        and 255, what cairo's RGB24 surface holds behind an opaque paint (tests/golden/getters: `frames`, tests/golden/views)."""
         f = getattr(self, "_frame", None)
         if f is None:
             self.draw()
             f = self._frame
+        if f.ndim == 3:
+            return f.tobytes()
         px = np.repeat(f[:, :, None], 4, axis=2)
         px[:, :, 3] = 255
         return px.tobytes()

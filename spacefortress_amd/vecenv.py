@@ -419,6 +419,50 @@ class SFVecEnv:
         _lib.check(self._L.sf_render(self._h, _lib.OBS_TYPES[mode], C.c_void_p(out.data_ptr()), stride, self._stream()))
         return out
 
+    def render_view(self, width=-1, height=-1, viewport=(0, 0, -1, -1), lw=2.0, grayscale=False, format="bgrx", lanes=None, out=None,
+                    glyphs=None):
+        """Frames of the CURRENT state in a VIEW (sfmi.h: sf_render_view): what the reference's Game(config, lw, grayscale, width,
+        height, viewport).draw() leaves in pb_pixels, with its defaults (viewport size -1: the config's 710 x 626; width /
+        height -1: the viewport's size), up to 1.0 pixel per user unit.  format "bgrx": uint8 [n, H, W, 4] (pb_pixels' bytes),
+        "rgb": [n, H, W, 3] (video tools, gym's rgb_array), "gray": [n, H, W] (grey views only).  lanes: None (all), an int or
+        a range of consecutive lanes.  glyphs: dict(alpha, layout, x0) as score_glyphs() gives, the atlas of this view; None: the
+        built-in one at 1.0 pixel per unit and a whole viewport offset, else the seven-segment fallback.  Reads the state only."""
+        if format not in _lib.VIEW_FORMATS:
+            raise ValueError("format must be one of %s" % (sorted(_lib.VIEW_FORMATS),))
+        if lanes is None:
+            first, n = 0, self.num_envs
+        elif isinstance(lanes, range):
+            if lanes.step != 1 and len(lanes) > 1:
+                raise ValueError("lanes must be consecutive")
+            first, n = lanes.start, len(lanes)
+        else:
+            first, n = int(lanes), 1
+        v = _lib.View(int(width), int(height), float(viewport[0]), float(viewport[1]), float(viewport[2]), float(viewport[3]), float(lw),
+                      1 if grayscale else 0, _lib.VIEW_FORMATS[format])
+        keep = None
+        if glyphs is not None:
+            a = np.ascontiguousarray(glyphs["alpha"], np.uint8)
+            gw, gh, adv, y0 = (int(x) for x in glyphs["layout"])
+            if a.shape != (11, gh, gw):
+                raise ValueError("alpha must be uint8 [11, gh, gw] = [11, %d, %d]" % (gh, gw))
+            g = _lib.ScoreGlyphs(gw, gh, adv, y0)
+            xs = np.broadcast_to(np.asarray(glyphs["x0"], np.int16), (11, 10))
+            for i in range(11):
+                for j in range(10):
+                    g.x0[i][j] = int(xs[i, j])
+            v.glyphs, v.glyph_alpha, keep = C.pointer(g), a.ctypes.data_as(C.c_void_p), (g, a)
+        w, h = C.c_int32(), C.c_int32()
+        _lib.check(self._L.sf_view_size(self._h, C.byref(v), C.byref(w), C.byref(h)))  # (the batch's config)
+        shape = (h.value, w.value) + ((4,) if format == "bgrx" else (3,) if format == "rgb" else ())
+        if out is None:
+            out = torch.empty((n,) + shape, dtype=torch.uint8, device=self.device)
+        if tuple(out.shape) != (n,) + shape or out.dtype != torch.uint8 or out.device != self.device or (n and not out[0].is_contiguous()):
+            raise ValueError("out must be uint8 %s on %s with contiguous frames" % (((n,) + shape), self.device))
+        stride = out.stride(0) if n > 1 else 0
+        _lib.check(self._L.sf_render_view(self._h, C.byref(v), first, n, C.c_void_p(out.data_ptr()), stride, self._stream()))
+        del keep
+        return out
+
     def draw_records(self, from_state=False):
         """Diagnostics: the envs' draw records (sfmi.h: sf_draw_records) as uint8 [N, 432] -- what the frame kernel reads
         instead of the state.  from_state=True rebuilds them from the state first (what a frame does after reset() /
