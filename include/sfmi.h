@@ -15,9 +15,9 @@
  *     `stream` is a hipStream_t passed as void* (NULL = the default stream).
  *   - every *_dev pointer is DEVICE memory owned by the caller (PyTorch); the
  *     library borrows it for the duration of the stream work it enqueues and
- *     makes no allocation after sf_create (two exceptions: the first image frame
+ *     makes no allocation after sf_create (three exceptions: the first image frame
  *     of a batch allocates that batch's render caches; sf_render_view the tables
- *     of a view it has not drawn lately).
+ *     of a view it has not drawn lately; sf_copy_lanes its scratch rows).
  *   - calls are asynchronous and stream-ordered; nothing synchronises unless
  *     documented (sf_get_field / sf_episode_stats do).
  *   - every function returns an sf_status (0 = ok, < 0 = error);
@@ -343,6 +343,58 @@ int sf_set_field(sf_batch* b, int field_id, const void* host, size_t bytes);
  * SRC/pymodule.cpp:24-48,78-105; spacefortress_amd/durations.py keeps SRC/game.hh:98-101's four vectors with it).  Every
  * field but missile_x / missile_y / missile_angle (SF_ERR_FIELD: their per-slot view is made on the host's demand). */
 int sf_get_field_dev(sf_batch* b, int field_id, void* dev, size_t bytes, void* stream);
+
+/* ---- lane states: save, restore and fork single envs of a batch on the device -- ALE's cloneState / restoreState for a
+ *      batch, without a round trip through host memory.  A LANE-STATE ROW is SF_LANE_STATE_BYTES (sf_lane_state_bytes()) per
+ *      env, the same format for every batch (no batch is needed to ask):
+ *        bytes    0 .. 15     header: uint32 SF_LANE_STATE_MAGIC | SF_LANE_STATE_VERSION, uint32 preset (bit 0 autoturn,
+ *                             bit 1 shaped scoring), uint32 seed and uint32 spawn_table_len of the batch it came from (the
+ *                             spawn table is a function of those two: a row continues the same libc spawn stream only in a
+ *                             batch with the same table)
+ *                 16 .. 127   the env's seven 16-byte chunks of sf_layout.h's one-slot groups (ship position, velocity, the
+ *                             packed timer / counter words, score, misc, small): every scalar field of sf_field_info
+ *                             including the packed per-episode counters, ep_return, ep_kills, prev_vlner, the key flags
+ *                             and counters and spawn_cursor
+ *                 128 .. 767  its shells: 20 (x, y) then 20 (vx, vy), doubles
+ *                 768 .. 1087 its missiles by slot (x, y), doubles; zero where the slot has none
+ *                 1088 .. 1135 their headings as uint16 [20], then zeros
+ *      A row holds nothing that belongs to the batch or the policy: the episode accumulators (sf_episode_stats), the sticky
+ *      overflow count (sf_check_state), the action sampler (sf_seed_actions) and VecNormalize's statistics stay with the
+ *      destination batch.
+ *      Every call below is asynchronous on `stream`, never synchronises, and can be captured in a HIP graph.  Index arrays are
+ *      DEVICE int32 or int64 (idx_type SF_ACT_I32 / SF_ACT_I64; the row indices of sf_load_lanes have the same type);
+ *      lanes_dev NULL = lanes 0 .. n-1.
+ *      sf_save_lanes: row k of rows_dev [n][SF_LANE_STATE_BYTES] = the state of lane lanes[k].  A lane outside the batch gets a
+ *        zero header (no batch takes the row) and is counted.
+ *      sf_load_lanes: lane lanes[k] takes row row_idx[k] of rows_dev [n_rows][...] (row_idx_dev NULL: row k).  One row into
+ *        many lanes (forking) is the main use.  A destination named twice: the LAST occurrence wins.  A row whose header is not
+ *        this batch's, a lane outside [0, n_envs) or a row outside [0, n_rows) is skipped -- its lane keeps its state -- and
+ *        counted on the device.  obs_dev (may be NULL; symbolic observation types): [n_envs][obs_dim] of the batch's type,
+ *        each restored lane's row at its own index = what the source lane's last step (or sf_reset) returned for that state,
+ *        bit for bit (a new game's, time 0, as sf_reset gives it, SF_FLAG_REF_RESET_OBS included).  Image batches draw with
+ *        sf_render afterwards: their draw records are rebuilt from the state before the next frame.
+ *      sf_copy_lanes: lane dst_lanes[k] of dst takes the state of lane src_lanes[k] of src, as if every source were read before
+ *        any destination is written (src == dst with overlapping lanes works).  The batches must have the same preset, seed and
+ *        spawn table and live on the same device: else SF_ERR_ARG before anything is launched.  The copy goes through scratch
+ *        rows the destination batch owns, allocated by its first call with that many lanes (a capture needs one eager call
+ *        with at least as many first: inside a capture a call that would allocate is SF_ERR_ARG).
+ *      sf_check_lanes: reads and clears the refusal count of the batch (synchronises `stream`): SF_ERR_ARG while it was
+ *        not zero.
+ *      Not part of a row: the frame stacks and rollout storage of the wrappers (caller data: copy them by tensor indexing).
+ *      The render-order hint words of image batches (sf_set_render_order_hint) are left as they are: they decide when a
+ *      frame is drawn, never what it holds.  DESIGN.md "Lane states" lists every per-tile and per-lane buffer. ---- */
+#define SF_LANE_STATE_BYTES 1136
+#define SF_LANE_STATE_MAGIC 0x53464C00u /* "SFL" << 8 */
+#define SF_LANE_STATE_VERSION 1
+int sf_lane_state_bytes(void);
+int sf_save_lanes(sf_batch* b, const void* lanes_dev, int idx_type, int n, void* rows_dev, void* stream);
+int sf_load_lanes(sf_batch* b, const void* lanes_dev, int idx_type, int n, const void* rows_dev, int n_rows,
+                  const void* row_idx_dev, void* obs_dev, void* stream);
+int sf_copy_lanes(sf_batch* dst, const void* dst_lanes_dev, sf_batch* src, const void* src_lanes_dev, int idx_type, int n,
+                  void* obs_dev, void* stream);
+int sf_check_lanes(sf_batch* b, void* stream);
+/* the header a row from this batch carries (uint32[4], host memory; no GPU work) */
+int sf_lane_state_header(const sf_batch* b, uint32_t* header);
 
 /* ---- episode statistics (host side of rl/train.py:81,84-88,161-164): accumulated on the device
  *      at every episode end; this copies them out (synchronises `stream`) and optionally clears.

@@ -27,6 +27,11 @@ FLAG_REAL_SHELL_COUNT = 2
 FLAG_NO_AUTO_RESET = 4
 FLAG_REF_RESET_OBS = 8
 EPISODE_STATS_LEN = 8
+# lane-state rows (sfmi.h: sf_save_lanes): SF_LANE_STATE_BYTES per env, a 16-byte header of four uint32 words
+LANE_STATE_BYTES = 1136
+LANE_STATE_MAGIC = 0x53464C00
+LANE_STATE_VERSION = 1
+ACT_I32, ACT_I64 = 4, 8
 
 
 class SfmiError(RuntimeError):
@@ -144,6 +149,12 @@ SYMBOLS = {
     "sf_resize_area_tab": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_resize_area_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "sf_set_render_order_hint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "sf_lane_state_bytes": (C.c_int, []),
+    "sf_lane_state_header": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "sf_save_lanes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sf_load_lanes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sf_copy_lanes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sf_check_lanes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sf_last_error": (C.c_char_p, []),
     "sf_version": (C.c_int, []),
     "sf_build_id": (C.c_char_p, []),

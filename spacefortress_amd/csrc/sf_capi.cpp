@@ -64,6 +64,17 @@ struct sf_batch {
   // out first: a caller that alternates between a few views (a recorder's colour view and an agent's grey one) makes each once
   struct ViewCache* views;
   unsigned long long view_clock;
+  // lane states (sfmi.h: sf_save_lanes ...): what the header of a row says of this batch, and the load's device bookkeeping --
+  // lane -> k map (all -1 between calls), per tile a flag and the list of tiles a call touches, the list's length, the
+  // refusal count (sf_check_lanes); sf_copy_lanes' scratch rows (lrows_cap of them, made by the first copy that needs them)
+  uint32_t seed;
+  long spawn_len;
+  unsigned char* d_lanes;
+  int* d_lmap;
+  unsigned *d_ltflag, *d_ltlist, *d_ltcount;
+  unsigned long long* d_lrefused;
+  unsigned char* d_lrows;
+  long lrows_cap;
 };
 
 constexpr int kViewCache = 4;
@@ -290,6 +301,20 @@ extern "C" int sf_create(const sf_create_params* p, sf_batch** out) {
   HIP_TRY_FREE(hipMemcpy(b->d_acc, kAccInit, sizeof(kAccInit), hipMemcpyHostToDevice));
   HIP_TRY_FREE(hipMalloc((void**)&b->d_actrec, (size_t)(lanes / 64) * 16));
   {
+    // the lane-state load's bookkeeping: map [lanes] int32 (-1), tile flags and list [lanes / 64], list length, refusals
+    const size_t tiles = (size_t)(lanes / 64), map_b = (size_t)lanes * 4, rest = tiles * 8 + 16;
+    HIP_TRY_FREE(hipMalloc((void**)&b->d_lanes, map_b + rest));
+    HIP_TRY_FREE(hipMemset(b->d_lanes, 0xFF, map_b));
+    HIP_TRY_FREE(hipMemset(b->d_lanes + map_b, 0, rest));
+    b->d_lmap = (int*)b->d_lanes;
+    b->d_ltflag = (unsigned*)(b->d_lanes + map_b);
+    b->d_ltlist = b->d_ltflag + tiles;
+    b->d_lrefused = (unsigned long long*)(b->d_ltlist + tiles);
+    b->d_ltcount = (unsigned*)(b->d_lrefused + 1);
+    b->seed = p->seed;
+    b->spawn_len = spawn_len;
+  }
+  {
     // image observation tables (sf_image.cpp): 11 KB, built for every batch so that sf_render works
     // whatever obs_type the batch steps with (the reference's render(), ENV:190-193)
     static_assert(SF_IMG_W == SF_IMAGE_W && SF_IMG_H == SF_IMAGE_H && SF_OUT == SF_IMAGE_OUT, "sfmi.h vs sf_raster.h");
@@ -460,6 +485,8 @@ extern "C" int sf_destroy(sf_batch* b) {
   if (b->d_spawn) (void)hipFree(b->d_spawn);
   if (b->d_acc) (void)hipFree(b->d_acc);
   if (b->d_actrec) (void)hipFree(b->d_actrec);
+  if (b->d_lanes) (void)hipFree(b->d_lanes);
+  if (b->d_lrows) (void)hipFree(b->d_lrows);
   if (b->d_scratch) (void)hipFree(b->d_scratch);
   if (b->d_ms_pos) (void)hipFree(b->d_ms_pos);
   if (b->d_ms_ang) (void)hipFree(b->d_ms_ang);
@@ -1302,5 +1329,146 @@ extern "C" int sf_render_view(sf_batch* b, const sf_view* view, int first_lane, 
                        b->d_consts + SF_LDS_TRIG, b->d_arcs, v.d_circle, r.circle_k, v.d_bg, v.bg_stride, v.d_glyphs, out_dev,
                        lane_stride};
   HIP_TRY(sf_launch_render_view(L, (hipStream_t)stream));
+  return SF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// lane states (sfmi.h): rows of SF_LANE_STATE_BYTES <-> lanes, on the device (sf_kernels.hip: sf_lanes_*_kernel)
+namespace {
+void lane_header(const sf_batch* b, uint32_t h[4]) {
+  h[0] = SF_LANE_STATE_MAGIC | SF_LANE_STATE_VERSION;
+  h[1] = (b->autoturn ? 1u : 0u) | (b->preset.shaped ? 2u : 0u);
+  h[2] = b->seed;
+  h[3] = (uint32_t)b->spawn_len;
+}
+// SF_ACT_I32 -> 0, SF_ACT_I64 -> 1, else -1
+int lane_idx64(int idx_type) { return idx_type == SF_ACT_I32 ? 0 : (idx_type == SF_ACT_I64 ? 1 : -1); }
+int lane_args(const sf_batch* b, const void* lanes_dev, int idx_type, int n, const char* who) {
+  if (!b || n < 0 || lane_idx64(idx_type) < 0) {
+    sf_set_error("%s: needs a batch, n >= 0 and idx_type SF_ACT_I32 or SF_ACT_I64", who);
+    return SF_ERR_ARG;
+  }
+  if (!lanes_dev && n > b->n_envs) {
+    sf_set_error("%s: no lane list and n = %d > n_envs = %d", who, n, b->n_envs);
+    return SF_ERR_ARG;
+  }
+  return SF_OK;
+}
+int lane_obs_ok(const sf_batch* b, const void* obs_dev, const char* who) {
+  if (obs_dev && (is_image(b) || b->args.obs_type == SF_OBS_NONE)) {
+    sf_set_error("%s: obs_dev is for the symbolic observation types; image batches draw with sf_render afterwards", who);
+    return SF_ERR_ARG;
+  }
+  return SF_OK;
+}
+int load_rows(sf_batch* b, const void* lanes_dev, int idx64, int n, const void* rows_dev, long n_rows, const void* row_idx_dev,
+              void* obs_dev, hipStream_t stream) {
+  uint32_t h[4];
+  lane_header(b, h);
+  HIP_TRY(sf_launch_lanes_load(b->args, lanes_dev, idx64, n, (const unsigned char*)rows_dev, row_idx_dev, n_rows, h, b->d_lmap,
+                               b->d_ltflag, b->d_ltlist, b->d_ltcount, b->d_lrefused, obs_dev, stream));
+  b->draw_current = false;  // (the next frame rebuilds the draw records from the state: sf_drawrec_kernel)
+  return SF_OK;
+}
+}  // namespace
+
+extern "C" int sf_lane_state_bytes(void) { return SF_LANE_STATE_BYTES; }
+
+extern "C" int sf_lane_state_header(const sf_batch* b, uint32_t* header) {
+  if (!b || !header) {
+    sf_set_error("sf_lane_state_header: null argument");
+    return SF_ERR_ARG;
+  }
+  lane_header(b, header);
+  return SF_OK;
+}
+
+extern "C" int sf_save_lanes(sf_batch* b, const void* lanes_dev, int idx_type, int n, void* rows_dev, void* stream) {
+  int rc = lane_args(b, lanes_dev, idx_type, n, "sf_save_lanes");
+  if (rc != SF_OK) return rc;
+  if (n > 0 && !rows_dev) {
+    sf_set_error("sf_save_lanes: null rows");
+    return SF_ERR_ARG;
+  }
+  DeviceGuard guard(b->device);
+  SF_FLUSH_VIEW(b, stream);
+  uint32_t h[4];
+  lane_header(b, h);
+  HIP_TRY(sf_launch_lanes_save(b->d_state, b->n_envs, lanes_dev, lane_idx64(idx_type), n, (unsigned char*)rows_dev, h, b->d_lrefused,
+                               (hipStream_t)stream));
+  return SF_OK;
+}
+
+extern "C" int sf_load_lanes(sf_batch* b, const void* lanes_dev, int idx_type, int n, const void* rows_dev, int n_rows,
+                             const void* row_idx_dev, void* obs_dev, void* stream) {
+  int rc = lane_args(b, lanes_dev, idx_type, n, "sf_load_lanes");
+  if (rc == SF_OK) rc = lane_obs_ok(b, obs_dev, "sf_load_lanes");
+  if (rc != SF_OK) return rc;
+  if (n_rows < 0 || (n > 0 && (!rows_dev || n_rows == 0))) {
+    sf_set_error("sf_load_lanes: needs rows (n_rows = %d)", n_rows);
+    return SF_ERR_ARG;
+  }
+  if (!row_idx_dev && n > n_rows) {
+    sf_set_error("sf_load_lanes: no row list and n = %d > n_rows = %d", n, n_rows);
+    return SF_ERR_ARG;
+  }
+  DeviceGuard guard(b->device);
+  SF_FLUSH_VIEW(b, stream);
+  return load_rows(b, lanes_dev, lane_idx64(idx_type), n, rows_dev, n_rows, row_idx_dev, obs_dev, (hipStream_t)stream);
+}
+
+extern "C" int sf_copy_lanes(sf_batch* dst, const void* dst_lanes_dev, sf_batch* src, const void* src_lanes_dev, int idx_type, int n,
+                             void* obs_dev, void* stream) {
+  int rc = lane_args(dst, dst_lanes_dev, idx_type, n, "sf_copy_lanes");
+  if (rc == SF_OK) rc = lane_args(src, src_lanes_dev, idx_type, n, "sf_copy_lanes");
+  if (rc == SF_OK) rc = lane_obs_ok(dst, obs_dev, "sf_copy_lanes");
+  if (rc != SF_OK) return rc;
+  uint32_t hd[4], hs[4];
+  lane_header(dst, hd);
+  lane_header(src, hs);
+  if (memcmp(hd, hs, sizeof(hd)) != 0 || dst->device != src->device) {
+    sf_set_error("sf_copy_lanes: the batches differ in preset, seed, spawn table or device (preset %u / %u, seed %u / %u, "
+                 "table %u / %u, device %d / %d)", hd[1], hs[1], hd[2], hs[2], hd[3], hs[3], dst->device, src->device);
+    return SF_ERR_ARG;
+  }
+  if (n == 0) return SF_OK;
+  DeviceGuard guard(dst->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (dst->lrows_cap < n) {  // scratch rows: made here, outside any capture
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cs));
+    if (cs != hipStreamCaptureStatusNone) {
+      sf_set_error("sf_copy_lanes: the batch's scratch holds %ld rows and %d are needed; make one eager call with that many "
+                   "lanes before capturing", dst->lrows_cap, n);
+      return SF_ERR_ARG;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (dst->d_lrows) HIP_TRY(hipFree(dst->d_lrows));
+    dst->d_lrows = nullptr;
+    dst->lrows_cap = 0;
+    HIP_TRY(hipMalloc((void**)&dst->d_lrows, (size_t)n * SF_LANE_STATE_BYTES));
+    dst->lrows_cap = n;
+  }
+  SF_FLUSH_VIEW(src, st);
+  SF_FLUSH_VIEW(dst, st);
+  const int idx64 = lane_idx64(idx_type);
+  // every source into the scratch rows first (a refused source lane leaves a row no batch takes), then the loads
+  HIP_TRY(sf_launch_lanes_save(src->d_state, src->n_envs, src_lanes_dev, idx64, n, dst->d_lrows, hs, dst->d_lrefused, st));
+  return load_rows(dst, dst_lanes_dev, idx64, n, dst->d_lrows, n, nullptr, obs_dev, st);
+}
+
+extern "C" int sf_check_lanes(sf_batch* b, void* stream) {
+  if (!b) return SF_ERR_ARG;
+  DeviceGuard guard(b->device);
+  unsigned long long bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, b->d_lrefused, sizeof(bad), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  if (bad) {
+    HIP_TRY(hipMemsetAsync(b->d_lrefused, 0, sizeof(bad), (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    sf_set_error("%llu lane states were refused (lane or row index out of range, or a row from another preset / seed / spawn "
+                 "table) and their lanes left as they were", bad);
+    return SF_ERR_ARG;
+  }
   return SF_OK;
 }

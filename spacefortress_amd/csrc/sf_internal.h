@@ -28,6 +28,15 @@ hipError_t sf_launch_slots_to_mpool(unsigned char* state, long lanes, int n_envs
 hipError_t sf_launch_mslot_component(void* sl_pos, int32_t* sl_ang, long total, int which, void* linear, int to_linear,
                                      hipStream_t stream);
 
+// lane states (sfmi.h: sf_save_lanes / sf_load_lanes): rows of SF_LANE_STATE_BYTES <-> lanes.  idx64: the index arrays are int64
+// (else int32).  Load: map = [lanes] int32 all -1, tflag = [lanes / 64] all 0, tlist = [lanes / 64], tcount = one word -- the
+// launches leave map and tflag as they found them; refused counts the rejected (lane, row) pairs
+hipError_t sf_launch_lanes_save(const unsigned char* state, int n_envs, const void* lanes, int idx64, int n, unsigned char* rows,
+                                const uint32_t header[4], unsigned long long* refused, hipStream_t stream);
+hipError_t sf_launch_lanes_load(const SfKernelArgs& a, const void* lanes, int idx64, int n, const unsigned char* rows, const void* row_idx,
+                                long n_rows, const uint32_t header[4], int* map, unsigned* tflag, unsigned* tlist, unsigned* tcount,
+                                unsigned long long* refused, void* obs, hipStream_t stream);
+
 hipError_t sf_launch_group_copy(const unsigned char* state, int n_envs, int group, unsigned char* linear,
                                 hipStream_t stream);
 

@@ -2268,3 +2268,238 @@ hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, con
 #undef SF_GO2
   return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// Lane states (sfmi.h: sf_save_lanes / sf_load_lanes / sf_copy_lanes): one env's whole game state as a row of
+// SF_LANE_STATE_BYTES, independent of the lane and the tile it came from.  A row is 71 pieces of 16 bytes:
+//   0        header (SF_LANE_STATE_MAGIC | version, preset, seed, spawn table length) -- sfmi.h
+//   1 .. 7   the lane's chunks of ship_pos, ship_vel, timers_a, timers_b, score, misc, small (the tile's pool count that rides
+//            above the missile mask is cleared: it belongs to the tile)
+//   8 .. 47  its shell_pos / shell_vel chunks, slots 0 .. 19 each
+//   48 .. 67 its missiles by SLOT, (x, y) -- out of the tile's pool by owner and slot as sf_mpool_to_slots_kernel takes them;
+//            a slot without a missile is zero
+//   68 .. 70 their headings as uint16, slots 0 .. 19, then zeros
+// Save: one wave per row; the row's 71 pieces leave as one 1136-byte run of consecutive 16-byte stores.  Load: one wave
+// per destination tile the call touches, which rebuilds the tile's pool from the lanes it keeps and the rows it takes.
+static_assert(SF_LANE_STATE_BYTES == 16 * 71, "sfmi.h: the row's pieces");
+constexpr int kLsPieces = 71, kLsBase = 1, kLsShell = 8, kLsMis = 48, kLsAng = 68;
+static_assert(SF_G_ship_pos == 0 && SF_G_small == 6 && sfl::chunk_offset(SF_G_small) == 6 * 1024 &&
+                  sfl::chunk_offset(SF_G_shell_vel) == sfl::chunk_offset(SF_G_shell_pos, SF_NSLOT),
+              "the row copies the seven one-slot groups, then the shell groups, as runs of 1 KiB rows");
+
+__device__ __forceinline__ long sf_lane_index(const void* idx, int idx64, long k) {
+  return idx64 ? (long)reinterpret_cast<const long long*>(idx)[k] : (long)reinterpret_cast<const int*>(idx)[k];
+}
+
+// piece p (1 .. 47) of lane l: its byte offset inside the tile
+__device__ __forceinline__ unsigned sf_ls_chunk_off(int p, unsigned l) {
+  return (p < kLsShell ? (unsigned)(p - kLsBase) * 1024u : (unsigned)sfl::chunk_offset(SF_G_shell_pos) + (unsigned)(p - kLsShell) * 1024u) +
+         16u * l;
+}
+
+__global__ __launch_bounds__(64) void sf_lanes_save_kernel(const unsigned char* state, int n_envs, const void* lanes, int idx64,
+                                                          unsigned char* rows, u4_t header, unsigned long long* refused) {
+  __shared__ d2_t mpos[SF_NSLOT];
+  __shared__ unsigned mang[SF_NSLOT];
+  const long k = blockIdx.x;
+  const unsigned lane = threadIdx.x;
+  const long e = lanes ? sf_lane_index(lanes, idx64, k) : k;
+  unsigned char* const row = rows + k * (long)SF_LANE_STATE_BYTES;
+  if (e < 0 || e >= n_envs) {  // (uniform) no such lane: a row no batch takes
+    if (lane == 0) {
+      *reinterpret_cast<u4_t*>(row) = u4_t{0u, 0u, 0u, 0u};
+      atomicAdd(refused, 1ull);
+    }
+    return;
+  }
+  const unsigned char* const tb = state + (e >> 6) * sfl::kTileBytes;
+  const unsigned l = (unsigned)(e & 63);
+  if (lane < SF_NSLOT) {
+    mpos[lane] = d2_t{0.0, 0.0};
+    mang[lane] = 0u;
+  }
+  __syncthreads();
+  const unsigned n_pool = SF_LD(unsigned, SF_CHUNK(misc, 0), 16u * l + 8u) >> SF_MPOOL_SHIFT;
+  for (unsigned i = lane; i < n_pool; i += 64) {
+    const unsigned m = SF_LD(unsigned, SF_CHUNK(missile_meta, 0), i * 4u);
+    if (SF_MM_OWNER(m) == l) {
+      mpos[SF_MM_SLOT(m)] = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), i * 16u);
+      mang[SF_MM_SLOT(m)] = SF_MM_ANGLE(m);
+    }
+  }
+  __syncthreads();
+  for (int p = (int)lane; p < kLsPieces; p += 64) {
+    u4_t v;
+    if (p == 0) {
+      v = header;
+    } else if (p < kLsMis) {
+      v = SF_LD(u4_t, tb, sf_ls_chunk_off(p, l));
+      if (p == kLsBase + SF_G_misc) v.z &= SF_MASK_LOW;  // (the tile's pool count: not the lane's)
+    } else if (p < kLsAng) {
+      v = __builtin_bit_cast(u4_t, mpos[p - kLsMis]);
+    } else {
+      unsigned w[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int s = 8 * (p - kLsAng) + 2 * j;
+        w[j] = (s < SF_NSLOT ? mang[s] : 0u) | ((s + 1 < SF_NSLOT ? mang[s + 1] : 0u) << 16);
+      }
+      v = u4_t{w[0], w[1], w[2], w[3]};
+    }
+    *reinterpret_cast<u4_t*>(row + 16 * p) = v;
+  }
+}
+
+// Load, pass 1: every (lane, row) pair of the call is checked -- lane inside the batch, row index inside the rows, the row's
+// header the batch's -- and counted where it is not; the accepted ones file k into map[lane] with atomicMax (the LAST
+// occurrence of a lane wins) and their tile into the list of tiles pass 2 visits (once each: the tile's flag).
+__global__ __launch_bounds__(SF_BLOCK) void sf_lanes_mark_kernel(int n_envs, const void* lanes, int idx64, int n,
+                                                                const unsigned char* rows, const void* row_idx, long n_rows, u4_t header,
+                                                                int* map, unsigned* tflag, unsigned* tlist, unsigned* tcount,
+                                                                unsigned long long* refused) {
+  const long k = (long)blockIdx.x * SF_BLOCK + threadIdx.x;
+  if (k >= n) return;
+  const long e = lanes ? sf_lane_index(lanes, idx64, k) : k;
+  const long r = row_idx ? sf_lane_index(row_idx, idx64, k) : k;
+  bool ok = e >= 0 && e < n_envs && r >= 0 && r < n_rows;
+  if (ok) {
+    const u4_t h = *reinterpret_cast<const u4_t*>(rows + r * (long)SF_LANE_STATE_BYTES);
+    ok = h.x == header.x && h.y == header.y && h.z == header.z && h.w == header.w;
+  }
+  if (!ok) {
+    atomicAdd(refused, 1ull);
+    return;
+  }
+  atomicMax(&map[e], (int)k);
+  if (atomicExch(&tflag[e >> 6], 1u) == 0u) tlist[atomicAdd(tcount, 1u)] = (unsigned)(e >> 6);
+}
+
+// Load, pass 2: one wave per listed tile (a grid-stride loop over the list).  The lanes that take a row get its chunks; the
+// tile's missile pool is rebuilt from the kept lanes' entries and the rows' slots, slot by slot with ballot + prefix count --
+// the order sf_slots_to_mpool_kernel gives -- and its count goes into every lane's missile word.  map / flags are left as
+// pass 1 found them (-1 / 0) for the next call.  obs (may be null): the restored lanes' observation rows, computed from the
+// restored state by the step kernel's functions (compute_extras with the bearings as the step computes them, write_obs).
+__global__ __launch_bounds__(64) void sf_lanes_load_kernel(SfKernelArgs a, const unsigned char* rows, const void* row_idx, int idx64,
+                                                          int* map, unsigned* tflag, const unsigned* tlist, const unsigned* tcount,
+                                                          void* obs) {
+  __shared__ d2_t spos[64][SF_NSLOT];
+  __shared__ unsigned short sang[64][SF_NSLOT];
+  __shared__ __attribute__((aligned(16))) unsigned char stage[7 * 1024];  // restored lanes' seven chunks, tile layout (obs)
+  const unsigned lane = threadIdx.x;
+  const unsigned n_tiles = *tcount;
+  for (unsigned ti = blockIdx.x; ti < n_tiles; ti += gridDim.x) {
+    const unsigned t = tlist[ti];
+    unsigned char* const tb = a.state + (size_t)t * sfl::kTileBytes;
+    const long e = (long)t * 64 + lane;
+    const int k = map[e];
+    const bool restored = k >= 0;
+    const unsigned char* const row =
+        restored ? rows + (row_idx ? sf_lane_index(row_idx, idx64, k) : (long)k) * (long)SF_LANE_STATE_BYTES : nullptr;
+    const unsigned long long rmask = __ballot(restored);
+    // everything that is read from the tile, first
+    const unsigned kept_mw = SF_LD(unsigned, SF_CHUNK(misc, 0), 16u * lane + 8u);
+    const unsigned n_pool = (unsigned)__builtin_amdgcn_readfirstlane(kept_mw) >> SF_MPOOL_SHIFT;
+    for (unsigned i = lane; i < n_pool; i += 64) {
+      const unsigned m = SF_LD(unsigned, SF_CHUNK(missile_meta, 0), i * 4u);
+      const unsigned o = SF_MM_OWNER(m);
+      if (!((rmask >> o) & 1ull)) {
+        spos[o][SF_MM_SLOT(m)] = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), i * 16u);
+        sang[o][SF_MM_SLOT(m)] = (unsigned short)SF_MM_ANGLE(m);
+      }
+    }
+    unsigned mask = e < a.n_envs ? (kept_mw & SF_MASK_LOW) : 0u;
+    if (restored) {
+#pragma unroll 4
+      for (int s = 0; s < SF_NSLOT; s++) spos[lane][s] = SF_LD(d2_t, row, 16 * (kLsMis + s));
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const u4_t w = SF_LD(u4_t, row, 16 * (kLsAng + j));
+        const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int q = 0; q < 8; q++)
+          if (8 * j + q < SF_NSLOT) sang[lane][8 * j + q] = (unsigned short)(ww[q >> 1] >> (16 * (q & 1)));
+      }
+      mask = SF_LD(unsigned, row, 16 * (kLsBase + SF_G_misc) + 8) & SF_MASK_LOW;
+    }
+    __syncthreads();
+    // the pool, slot by slot (sf_slots_to_mpool_kernel's order)
+    unsigned wp = 0;
+    for (int s = 0; s < SF_NSLOT; s++) {
+      const bool live = (mask >> s) & 1u;
+      const unsigned long long b = __ballot(live);
+      const unsigned idx = wp + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+      wp += (unsigned)__popcll(b);
+      if (live) {
+        *reinterpret_cast<d2_t*>(SF_CHUNK(missile_pos, 0) + (size_t)idx * 16) = spos[lane][s];
+        *reinterpret_cast<unsigned*>(SF_CHUNK(missile_meta, 0) + (size_t)idx * 4) = SF_MM_PACK(sang[lane][s] & 511u, lane, s);
+      }
+    }
+    if (restored) {
+      // eight pieces in flight at a time: (the row and the tile might alias as far as the compiler knows -- one piece per
+      // round trip otherwise)
+      for (int p0 = kLsBase; p0 < kLsMis; p0 += 8) {
+        u4_t v[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = p0 + j < kLsMis ? SF_LD(u4_t, row, 16 * (p0 + j)) : u4_t{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          const int p = p0 + j;
+          if (p >= kLsMis) break;
+          if (p == kLsBase + SF_G_misc) v[j].z = mask | (wp << SF_MPOOL_SHIFT);
+          if (p < kLsShell) *reinterpret_cast<u4_t*>(stage + (p - kLsBase) * 1024 + 16 * lane) = v[j];
+          *reinterpret_cast<u4_t*>(tb + sf_ls_chunk_off(p, lane)) = v[j];
+        }
+      }
+    } else {
+      *reinterpret_cast<unsigned*>(SF_CHUNK(misc, 0) + 16u * lane + 8u) = mask | (wp << SF_MPOOL_SHIFT);
+      for (int g = 0; g < 7; g++) *reinterpret_cast<u4_t*>(stage + g * 1024 + 16 * lane) = u4_t{0u, 0u, 0u, 0u};  // (defined values below)
+    }
+    map[e] = -1;
+    if (lane == 0) tflag[t] = 0u;
+    if (obs != nullptr && a.obs_type != 3 && rmask != 0ull) {  // (uniform)
+      Lane L;
+      const Off o = {lane * 16u, lane * 8u, lane * 4u, lane * 2u, lane};
+      load_lane_early(stage, o, L);
+      unpack_lane_late(load_lane_late(stage, o), L);
+      // the bearings as the tick that made this state computed them: a new game's (time 0: sf_reset, an auto-reset) with the
+      // reset's atan2, any other with the step's table form (SF_FAST_ATAN); SF_FLAG_REF_RESET_OBS zeroes a new game's extras
+      const bool fresh = L.time == 0;
+      const double* atab = a.consts + SF_CONST_ATAB;
+      const double a_pos = fresh ? sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x)
+                                 : sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x, atab);
+      const double a_vel = fresh ? sf_atan2<false>(L.vy, L.vx) : (SF_FAST_ATAN ? sf_atan2_core(L.vy, L.vx, atab) : atan2(L.vy, L.vx));
+      Extras x = compute_extras(a, L, a_pos, a_vel);
+      if (fresh && a.ref_reset_obs) x = Extras{0.0, 0.0, 0.0};
+      if (restored) {
+        if (a.obs_f64)
+          write_obs<double>(a, (double*)obs + (size_t)e * a.obs_dim, L, x);
+        else
+          write_obs<float>(a, (float*)obs + (size_t)e * a.obs_dim, L, x);
+      }
+    }
+    __syncthreads();  // (the LDS rows are the next tile's)
+  }
+}
+
+hipError_t sf_launch_lanes_save(const unsigned char* state, int n_envs, const void* lanes, int idx64, int n, unsigned char* rows,
+                                const uint32_t header[4], unsigned long long* refused, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(sf_lanes_save_kernel, dim3((unsigned)n), dim3(64), 0, stream, state, n_envs, lanes, idx64, rows,
+                     u4_t{header[0], header[1], header[2], header[3]}, refused);
+  return hipGetLastError();
+}
+
+hipError_t sf_launch_lanes_load(const SfKernelArgs& a, const void* lanes, int idx64, int n, const unsigned char* rows, const void* row_idx,
+                                long n_rows, const uint32_t header[4], int* map, unsigned* tflag, unsigned* tlist, unsigned* tcount,
+                                unsigned long long* refused, void* obs, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(tcount, 0, sizeof(unsigned), stream);
+  if (e != hipSuccess) return e;
+  const u4_t h{header[0], header[1], header[2], header[3]};
+  hipLaunchKernelGGL(sf_lanes_mark_kernel, dim3((unsigned)((n + SF_BLOCK - 1) / SF_BLOCK)), dim3(SF_BLOCK), 0, stream, a.n_envs, lanes,
+                     idx64, n, rows, row_idx, n_rows, h, map, tflag, tlist, tcount, refused);
+  const long tiles = a.lanes / 64;
+  const unsigned grid = (unsigned)(n < tiles ? n : tiles);
+  hipLaunchKernelGGL(sf_lanes_load_kernel, dim3(grid), dim3(64), 0, stream, a, rows, row_idx, idx64, map, tflag, tlist, tcount, obs);
+  return hipGetLastError();
+}

@@ -93,6 +93,30 @@ class SSF_Env(_Base):
         self.last_action = action
         return obs[0], int(r[0]), bool(d[0]), bool(i[0])
 
+    # what the env's Game view keeps on the host between ticks (game.py): the tick's key calls and events, the duration vectors,
+    # the last observation (aim / vdir / ndist)
+    _G_HOST = ("_keys", "_calls", "_events", "thrust_durations", "shot_durations", "shot_intervals_invul", "shot_intervals_vul",
+               "_obs")
+
+    def clone_state(self):
+        """ALE's cloneState: this env's game as a LaneStates row on the device (sfmi.h: sf_save_lanes), plus what the env and its
+        Game view keep on the host.  restore_state(s) -- on this env or another SSF_Env of the same gametype and seed -- puts
+        it back: env.g.dump() and every Game getter then read what they read here."""
+        g = None if self._g is None else {k: (lambda v: list(v) if isinstance(v, list) else v)(getattr(self._g, k)) for k in self._G_HOST}
+        return {"lanes": self._vec.save_lanes(), "g": g, "last_action": self.last_action,
+                "actions_taken": dict(self.actions_taken)}
+
+    def restore_state(self, state):
+        """ALE's restoreState (see clone_state).  ValueError for a state from another gametype / seed."""
+        self._vec.load_lanes(state["lanes"].to(self._vec.device), check=True)
+        self.last_action = state["last_action"]
+        self.actions_taken = dict(state["actions_taken"])
+        if state["g"] is not None or self._g is not None:
+            self.g._new_game()
+            if state["g"] is not None:
+                for k, v in state["g"].items():
+                    setattr(self._g, k, list(v) if isinstance(v, list) else v)
+
     def render(self, mode="human", close=False):
         """ENV:180-198.  'rgb_array' returns game_gray_rgb, the grey frame replicated to [92, 90, 3];
         the pyglet window of mode 'human' is not part of this library."""

@@ -563,3 +563,103 @@ class SFVecEnv:
         # every packed field of every env has just been rewritten with values that fit (set_field range-checks): whatever had
         # wrapped is repaired, the sticky count of check_state() starts over (sfmi.h: sf_clear_state_errors)
         _lib.check(self._L.sf_clear_state_errors(self._h))
+
+    # ------------------------------------------------------------------ lane states (sfmi.h: sf_save_lanes ...)
+    def lane_state_header(self):
+        """The header a row from this batch carries: numpy uint32 [4] (magic | version, preset, seed, spawn table length)."""
+        h = np.zeros(4, np.uint32)
+        _lib.check(self._L.sf_lane_state_header(self._h, h.ctypes.data_as(C.c_void_p)))
+        return h
+
+    def _index(self, idx, what):
+        """(device tensor or None, count, idx type) for a lane / row index argument: None, a device int32 / int64 tensor (kept
+        as it is: graph capture), or anything torch.as_tensor takes (copied to the device)."""
+        if idx is None:
+            return None, None, None
+        if not (torch.is_tensor(idx) and idx.device == self.device and idx.dtype in (torch.int32, torch.int64)):
+            idx = torch.as_tensor(np.asarray(idx, np.int64).reshape(-1) if not torch.is_tensor(idx) else idx.reshape(-1),
+                                  dtype=torch.int64).to(self.device)
+        if idx.dim() != 1 or not idx.is_contiguous():
+            idx = idx.reshape(-1).contiguous()
+        return idx, idx.numel(), (_lib.ACT_I32 if idx.dtype == torch.int32 else _lib.ACT_I64)
+
+    @staticmethod
+    def _ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    def _obs_arg(self, obs):
+        if obs is None:
+            return None
+        if self.is_image or self.obs_type == "none":
+            raise ValueError("obs: image batches draw with render() after a load")
+        if not (torch.is_tensor(obs) and obs.device == self.device and obs.dtype == self.obs_dtype and obs.is_contiguous()
+                and obs.numel() == self.num_envs * self.obs_dim):
+            raise ValueError("obs must be a contiguous %s tensor [%d, %d] on %s" % (self.obs_dtype, self.num_envs, self.obs_dim,
+                                                                                   self.device))
+        return C.c_void_p(obs.data_ptr())
+
+    def save_lanes(self, lanes=None):
+        """The states of `lanes` (None: every lane) as LaneStates: uint8 [n, LANE_STATE_BYTES] on this device, written on the
+        current stream without synchronising.  A lane outside the batch gives a row no batch takes (check_lanes reports it)."""
+        from .lanes import LaneStates
+
+        idx, n, itype = self._index(lanes, "lanes")
+        if idx is None:
+            n, itype = self.num_envs, _lib.ACT_I32
+        rows = torch.empty((n, _lib.LANE_STATE_BYTES), dtype=torch.uint8, device=self.device)
+        _lib.check(self._L.sf_save_lanes(self._h, self._ptr(idx), itype, n, C.c_void_p(rows.data_ptr()), self._stream()))
+        h = self.lane_state_header()
+        return LaneStates(rows, self.gametype, int(h[2]), int(h[3]), _lib.LANE_STATE_VERSION,
+                          self._L.sf_build_id().decode())
+
+    def load_lanes(self, states, lanes=None, rows=None, obs=None, check=True):
+        """Lane lanes[k] (None: lane k) takes row rows[k] (None: row k) of `states` (LaneStates or a uint8 [n, bytes] tensor on
+        this device).  One row into many lanes forks it; a lane named twice takes its LAST row.  obs (symbolic types): the
+        [N, obs_dim] buffer that receives the restored lanes' observations -- what the source lane's last step returned.
+        check=True synchronises once and raises ValueError if a row was refused (another preset / seed / spawn table, an
+        index out of range; those lanes keep their state); check=False stays asynchronous (graph capture) and leaves the
+        count to check_lanes().  A recording is dropped (RuntimeError) and the duration log starts over, as with set_field."""
+        table = states.rows if hasattr(states, "rows") else states
+        if not (torch.is_tensor(table) and table.dtype == torch.uint8 and table.dim() == 2
+                and table.shape[1] == _lib.LANE_STATE_BYTES and table.device == self.device and table.is_contiguous()):
+            raise ValueError("load_lanes: the rows must be a contiguous uint8 [n, %d] tensor on %s (LaneStates.to(device))"
+                             % (_lib.LANE_STATE_BYTES, self.device))
+        lidx, n, itype = self._index(lanes, "lanes")
+        ridx, nr, rtype = self._index(rows, "rows")
+        if lidx is None and ridx is None:
+            n, itype = min(self.num_envs, table.shape[0]), _lib.ACT_I32
+        elif lidx is None:
+            n, itype = nr, rtype
+        elif ridx is not None and (nr != n or rtype != itype):
+            if nr != n:
+                raise ValueError("load_lanes: %d lanes and %d rows" % (n, nr))
+            ridx = ridx.to(lidx.dtype)
+        optr = self._obs_arg(obs)
+        self._touch()
+        _lib.check(self._L.sf_load_lanes(self._h, self._ptr(lidx), itype, n, C.c_void_p(table.data_ptr()), table.shape[0],
+                                         self._ptr(ridx), optr, self._stream()))
+        if check:
+            self.check_lanes()
+
+    def copy_lanes(self, dst_lanes, src_lanes, src=None, obs=None, check=True):
+        """Lane dst_lanes[k] of this batch takes the state of lane src_lanes[k] of `src` (None: this batch), as if every source
+        were read before any destination is written.  `src` must have this batch's preset, seed and spawn table (ValueError).
+        obs / check as in load_lanes."""
+        src = self if src is None else src
+        d, n, itype = self._index(dst_lanes, "dst_lanes")
+        s, ns, stype = src._index(src_lanes, "src_lanes")
+        if d is None or s is None:
+            raise ValueError("copy_lanes: name the lanes on both sides")
+        if ns != n:
+            raise ValueError("copy_lanes: %d destination and %d source lanes" % (n, ns))
+        if stype != itype:
+            s = s.to(d.dtype)
+        optr = self._obs_arg(obs)
+        self._touch()
+        _lib.check(self._L.sf_copy_lanes(self._h, self._ptr(d), src._h, self._ptr(s), itype, n, optr, self._stream()))
+        if check:
+            self.check_lanes()
+
+    def check_lanes(self):
+        """Raise ValueError if a lane state was refused since the last call (sfmi.h: sf_check_lanes; clears the count)."""
+        _lib.check(self._L.sf_check_lanes(self._h, self._stream()))
