@@ -430,14 +430,26 @@ int sf_normalizer_create(const sf_normalizer_params* params, sf_normalizer** out
 int sf_normalizer_destroy(sf_normalizer* z);
 /* VecNormalize.step_wait (obs + rewards) or .reset (obs only: reward pointers NULL).  obs_dev
  * [n_envs][obs_dim] -> obs_out_dev (may alias); reward_dev int32[n_envs] -> reward_out_dev float[n_envs].
- * frozen != 0: normalise with the statistics as they are (evaluation), update nothing. */
+ * frozen != 0: normalise with the statistics as they are (evaluation), update nothing.
+ * Conditioning: the batch variance is ONE-PASS in float64, sumsq / n - mean^2 (clamped at 0), so its absolute error is
+ * about mean(x^2) * 2^-53 times the depth of the summation (a few tens), i.e. a relative error of
+ * kappa * 2^-53 * depth with kappa = mean(x^2) / var of the column over the batch.  Game observations have kappa below
+ * 1e3 and normalise to within a float32 ulp of the exact result.  A column with mean 1000 and deviation 1e-2
+ * (kappa 1e10) came out up to 7e-7 from the exact result, one with deviation 3e-4 (kappa 1e13) up to 1e-3, once the
+ * running variance had come down to the data's own (profiles/norm_tests.md; bounds 3e-5 and 3e-2, tests/normref.py);
+ * beyond kappa 1e15 nothing is left of the batch variance.  Centre such inputs before they come here.
+ * HIP graphs: a call that updates the statistics (frozen == 0 and something to update) flips their double buffer on
+ * the HOST, which a replayed graph would not do: inside a stream capture it is refused with SF_ERR_ARG before anything
+ * is launched, and the capture can go on.  Frozen calls are plain stream work and can be captured and replayed.
+ * Results are run-to-run identical: the sums are added in a fixed order. */
 int sf_normalize(sf_normalizer* z, const void* obs_dev, void* obs_out_dev, const int32_t* reward_dev,
                  float* reward_out_dev, int frozen, void* stream);
 /* sf_step + sf_normalize with the batch reduction riding on the step kernel (its waves sum the observation
  * tile they have just written): step -> merge -> apply, one launch less than the two calls.  obs_dev is written
  * raw by the step and normalised in place; reward_dev keeps the raw int32 rewards (the trainer's episode
  * bookkeeping uses them), reward_out_dev gets the normalised ones.  The batch must have been created with a
- * 1-D observation type and the normalizer with its n_envs / obs_dim / obs_f64. */
+ * 1-D observation type and the normalizer with its n_envs / obs_dim / obs_f64.  Conditioning and HIP graphs as for
+ * sf_normalize: unless frozen, refused with SF_ERR_ARG inside a stream capture (the step is not launched either). */
 int sf_step_normalize(sf_batch* b, sf_normalizer* z, const void* actions_dev, int act_type, void* obs_dev,
                       int32_t* reward_dev, uint8_t* done_dev, uint8_t* info_dev, float* reward_out_dev, int frozen,
                       void* stream);

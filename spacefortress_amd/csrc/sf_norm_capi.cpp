@@ -35,6 +35,19 @@ struct DeviceGuard {
   }
 };
 
+// A call that updates the statistics flips z->parity on the host: a captured graph would replay the launch with the
+// buffers of the capture, not of the replay (sfmi.h).  Such a call inside a capture is refused before anything is launched.
+int refuse_in_capture(const char* who, hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_TRY(hipStreamIsCapturing(st, &cs));
+  if (cs != hipStreamCaptureStatusNone) {
+    sf_set_error("%s: a call that updates the running statistics cannot be captured in a HIP graph (the statistics' double "
+                 "buffer flips on the host at every such call); capture frozen calls only", who);
+    return SF_ERR_ARG;
+  }
+  return SF_OK;
+}
+
 int n_stats(const sf_normalizer* z) { return 2 * z->p.obs_dim + 4; }
 int n_sums(const sf_normalizer* z) { return 2 * (z->p.obs_dim + 1); }
 }  // namespace
@@ -114,6 +127,10 @@ extern "C" int sf_normalize(sf_normalizer* z, const void* obs_dev, void* obs_out
   DeviceGuard guard(z->p.device_id);
   const int k = z->parity;
   const int do_ob = (z->p.ob && obs_dev && !frozen) ? 1 : 0, do_ret = (z->p.ret && reward_dev && !frozen) ? 1 : 0;
+  if (do_ob || do_ret) {
+    const int rc = refuse_in_capture("sf_normalize", (hipStream_t)stream);
+    if (rc != SF_OK) return rc;
+  }
   HIP_TRY(sf_launch_normalize(z->p.ob ? obs_dev : nullptr, z->p.ob ? obs_out_dev : nullptr, z->p.obs_f64,
                               z->p.ret ? reward_dev : nullptr, z->p.ret ? reward_out_dev : nullptr, z->d_ret, z->p.n_envs,
                               z->p.obs_dim, z->p.gamma, z->p.epsilon, z->p.clipob, z->p.cliprew, do_ob, do_ret,
@@ -160,7 +177,9 @@ extern "C" int sf_step_normalize(sf_batch* b, sf_normalizer* z, const void* acti
   }
   DeviceGuard guard(z->p.device_id);
   int rows = 0;
-  int rc = sf_step_with_norm_partials(b, actions_dev, act_type, obs_dev, reward_dev, done_dev, info_dev, z->d_partials,
+  int rc = refuse_in_capture("sf_step_normalize", (hipStream_t)stream);
+  if (rc != SF_OK) return rc;
+  rc = sf_step_with_norm_partials(b, actions_dev, act_type, obs_dev, reward_dev, done_dev, info_dev, z->d_partials,
                                       z->p.ret ? z->d_ret : nullptr, z->p.gamma, &rows, stream);
   if (rc != SF_OK) return rc;
   const int k = z->parity;

@@ -23,6 +23,14 @@ class _Params(C.Structure):
 
 
 class SFVecNormalize:
+    """Numerics: the batch variance is one-pass in float64 (sumsq / n - mean^2, clamped at 0).  Its relative error is about
+    kappa * 2^-53 * 40 with kappa = mean(x^2) / var of a column over the batch: game observations (kappa below 1e3) come out
+    within a float32 ulp of the exact result; a column with mean 1000 and deviation 1e-2 (kappa 1e10) came out up to 7e-7
+    off, one with deviation 3e-4 (kappa 1e13) up to 1e-3 (profiles/norm_tests.md).  Centre such observations first.
+
+    HIP graphs: a training step updates the statistics, whose double buffer flips on the host, so it raises ValueError
+    inside a graph capture; with `training = False` a step can be captured and replayed."""
+
     def __init__(self, venv, ob=True, ret=True, clipob=10., cliprew=10., gamma=0.99, epsilon=1e-8):
         if len(venv.observation_space.shape) != 1:
             raise ValueError("VecNormalize is applied to 1-D observations (rl/train.py:35)")
