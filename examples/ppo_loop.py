@@ -9,6 +9,11 @@ The actor-critic below is a stand-in (two tanh layers, like rl/model.py's MLP br
 self-contained; the point is the data path: nothing crosses PCIe inside an iteration.
 
     python examples/ppo_loop.py --envs 4096 --iters 20
+
+--obs image runs the same loop on 84x84 frames, four to a stack (rl/train.py:38-41), over FrameRollout: every frame is kept
+once, the actor reads the current stack that step() returns and the minibatches are gathered as float32 by one launch each.
+
+    python examples/ppo_loop.py --obs image --envs 1024 --steps 32 --iters 5
 """
 import argparse
 import os
@@ -19,7 +24,7 @@ import torch
 import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from spacefortress_amd import DeviceRollout, SFVecEnv, SFVecNormalize  # noqa: E402
+from spacefortress_amd import DeviceRollout, FrameRollout, SFVecEnv, SFVecNormalize  # noqa: E402
 
 
 class ActorCritic(nn.Module):
@@ -33,8 +38,64 @@ class ActorCritic(nn.Module):
         return torch.distributions.Categorical(logits=self.pi(h)), self.v(h)
 
 
+class ConvActorCritic(nn.Module):
+    """A small stand-in for rl/model.py's CNN branch: [B, 4, 84, 84] float (0 .. 255) -> policy, value."""
+
+    def __init__(self, num_stack, n_actions):
+        super().__init__()
+        self.body = nn.Sequential(nn.Conv2d(num_stack, 16, 8, stride=4), nn.ReLU(), nn.Conv2d(16, 32, 4, stride=2), nn.ReLU(),
+                                  nn.Flatten(), nn.Linear(32 * 9 * 9, 128), nn.ReLU())
+        self.pi, self.v = nn.Linear(128, n_actions), nn.Linear(128, 1)
+
+    def forward(self, obs):
+        h = self.body(obs * (1.0 / 255.0))
+        return torch.distributions.Categorical(logits=self.pi(h)), self.v(h)
+
+
+def main_image(a):
+    """The image path: FrameRollout instead of DeviceRollout(env, T, num_stack=4); no `observations` tensor anywhere."""
+    env = SFVecEnv(a.envs, gametype=a.gametype, obs_type="image", spawn_stride=1)
+    ro = FrameRollout(env, a.steps, num_stack=4)
+    net = ConvActorCritic(4, env.n_actions).to(env.device)
+    opt = torch.optim.Adam(net.parameters(), lr=7e-4)
+    cur = ro.reset()
+    print("observation storage: %.1f MB (stacked: %.1f MB)" % (ro.nbytes() / 1e6, (a.steps + 1) * a.envs * 4 * 7056 / 1e6))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(a.iters):
+        for t in range(a.steps):
+            with torch.no_grad():
+                dist, value = net(cur.float())
+                action = dist.sample()
+            cur, _, _ = ro.step(t, action, value_pred=value, action_log_prob=dist.log_prob(action).unsqueeze(1))
+        with torch.no_grad():
+            next_value = net(cur.float())[1]
+        ro.compute_returns(next_value, True, 0.99, 0.95)
+        adv = ro.returns[:-1] - ro.value_preds[:-1]
+        adv = (adv - adv.mean()) / (adv.std() + 1e-5)
+        for _ in range(a.ppo_epochs):
+            for obs, _, act, ret, _, old_logp, adv_t in ro.feed_forward_generator(adv, a.mini_batches, obs_dtype=torch.float32):
+                dist, value = net(obs)
+                ratio = torch.exp(dist.log_prob(act.squeeze(1)).unsqueeze(1) - old_logp)
+                loss = (-torch.min(ratio * adv_t, torch.clamp(ratio, 0.9, 1.1) * adv_t).mean()
+                        + 0.5 * (value - ret).pow(2).mean() - 0.01 * dist.entropy().mean())
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+        ro.after_update()  # (the current stack is stack_at(0) of the next rollout: `cur` stays valid)
+        if (it + 1) % 5 == 0 or it == a.iters - 1:
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print("iter %3d  env-steps %9d  %.3g env-steps/s (whole loop)  mean final reward %.3f  kills %d" % (
+                it + 1, (it + 1) * a.steps * a.envs, (it + 1) * a.steps * a.envs / dt, float(ro.final_rewards.mean()),
+                ro.num_destruction))
+    env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--obs", choices=["features", "image"], default="features",
+                    help="features: normalised 1-D observations over DeviceRollout; image: frame stacks over FrameRollout")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=20, help="num_fwd_steps")
     ap.add_argument("--iters", type=int, default=20)
@@ -43,6 +104,8 @@ def main():
     ap.add_argument("--mini-batches", type=int, default=4)
     a = ap.parse_args()
     torch.manual_seed(0)
+    if a.obs == "image":
+        return main_image(a)
     envs = SFVecNormalize(SFVecEnv(a.envs, gametype=a.gametype, spawn_stride=1))
     ro = DeviceRollout(envs, a.steps)
     net = ActorCritic(envs.venv.obs_dim, envs.venv.n_actions).to(envs.device)

@@ -482,6 +482,34 @@ int sf_record_step_f32(int n, const float* reward_dev, const uint8_t* done_dev, 
 int sf_compute_returns(int num_steps, int n, const float* rewards, float* value_preds, const float* masks,
                        const float* next_value, float* returns, int use_gae, double gamma, double tau, void* stream);
 
+/* ---- The image rollout storage with every frame kept ONCE.  The trainer stores the whole frame stack of every step
+ *      (rl/train.py:38-41: obs_shape[0] * num_stack channels; :51-56,92-98: shift, `current_obs *= masks`, insert) and
+ *      samples minibatches from that (rl/storage.py:66-122: observations[:-1].view(-1, ...)[indices]), although S - 1 of the
+ *      S frames of step t + 1 are frames of step t.  A FRAME STORE holds, per env, rows = (S - 1) + T + 1 frames of 84 x 84
+ *      bytes -- S - 1 rows of history in front of the rollout's T + 1; store row r is the frame of step r - (S - 1) -- and
+ *      start_dev uint8 [rows][n_envs]: 1 where the frame is the first observation of a new game (masks[t] == 0; the reset
+ *      frame counts).  The stack of (t, e) is then a function of the store:
+ *          slot j (0 .. S-1) = row t + j of env e   if none of the rows t + j + 1 .. t + S - 1 of env e carries a start flag
+ *                            = 0                     otherwise                    (slot S - 1 is always row t + S - 1)
+ *      frames_dev: 16-byte aligned; env_stride / row_stride = bytes from a frame to the next env's frame of the same row / to
+ *      the same env's next row, multiples of 16 -- env-major [n_envs][rows][7056] or time-major [rows][n_envs][7056]
+ *      (sf_render writes a row of either: frames_dev + row * row_stride with that env_stride).  1 <= num_stack <= 16.
+ *      index_dev: n_samples flat transition indices t * n_envs + e in [0, T * n_envs), DEVICE int32 or int64 (idx_type
+ *      SF_ACT_I32 / SF_ACT_I64); NULL: the n_envs stacks of step `step` (0 .. T) in env order, n_samples = n_envs (the
+ *      actor's input; `step` is ignored otherwise).  out_dev [n_samples][S][84][84], 16-byte aligned, as uint8, float16 or
+ *      float32 (out_type; the conversion is exact, so the float outputs equal the uint8 one converted).  An index outside
+ *      the range is checked before any address is formed: its stack is zero and it is counted on the device.
+ *      Plain device pointers, launched on `stream` of the current device, never synchronises, can be captured in a HIP
+ *      graph.  sf_gather_errors reads that count (synchronises `stream`): *count_out (may be NULL) = indices out of range
+ *      since the count was last cleared, SF_ERR_ACTION while it is not zero; STICKY unless `clear`. ---- */
+#define SF_STACK_U8 1
+#define SF_STACK_F16 2
+#define SF_STACK_F32 4
+int sf_gather_stacks(const uint8_t* frames_dev, const uint8_t* start_dev, int n_envs, int rows, int num_stack,
+                     int64_t env_stride, int64_t row_stride, const void* index_dev, int idx_type, int64_t n_samples,
+                     int64_t step, void* out_dev, int out_type, void* stream);
+int sf_gather_errors(uint64_t* count_out, int clear, void* stream);
+
 /* ---- host-only helpers (usable without a GPU) ---- */
 typedef struct {
   int32_t width, height, game_time;

@@ -7,7 +7,7 @@ environment does, and fails loudly if the extension or the device is missing.
 """
 from ._lib import SfmiError, lib  # noqa: F401
 
-__all__ = ["SFVecEnv", "SSF_Env", "FrameStack", "SFVecNormalize", "DeviceRollout", "Replay", "LaneStates", "SfmiError", "lib"]
+__all__ = ["SFVecEnv", "SSF_Env", "FrameStack", "SFVecNormalize", "DeviceRollout", "FrameRollout", "Replay", "LaneStates", "SfmiError", "lib"]
 
 
 def __getattr__(name):
@@ -29,6 +29,9 @@ def __getattr__(name):
     if name == "DeviceRollout":
         from .rollout import DeviceRollout
         return DeviceRollout
+    if name == "FrameRollout":
+        from .frame_rollout import FrameRollout
+        return FrameRollout
     if name == "Replay":
         from .replay import Replay
         return Replay

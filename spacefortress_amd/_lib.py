@@ -32,6 +32,7 @@ LANE_STATE_BYTES = 1136
 LANE_STATE_MAGIC = 0x53464C00
 LANE_STATE_VERSION = 1
 ACT_I32, ACT_I64 = 4, 8
+STACK_U8, STACK_F16, STACK_F32 = 1, 2, 4  # SF_STACK_* (sfmi.h: sf_gather_stacks)
 
 
 class SfmiError(RuntimeError):
@@ -132,6 +133,9 @@ SYMBOLS = {
     "sf_record_step_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p]),
     "sf_record_step": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_void_p]),
     "sf_compute_returns": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "sf_gather_stacks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int64,
+                                   C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
+    "sf_gather_errors": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_void_p]),
     "sf_render_stack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sf_render_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "sf_frame_stack_clear": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),

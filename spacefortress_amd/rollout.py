@@ -38,7 +38,7 @@ class DeviceRollout:
             if env.obs_type != "image" or self.norm is not None:
                 raise ValueError("num_stack > 1 is for obs_type='image' (rl/train.py:38-39)")
             obs_shape = (self.num_stack,) + obs_shape[1:]
-        self.observations = torch.zeros((T + 1, n) + obs_shape, dtype=env.obs_dtype, device=dev)
+        self._alloc_observations((T + 1, n) + obs_shape)
         self.states = torch.zeros(T + 1, n, state_size, device=dev)
         self.rewards = torch.zeros(T, n, 1, device=dev)
         self.value_preds = torch.zeros(T + 1, n, 1, device=dev)
@@ -53,6 +53,13 @@ class DeviceRollout:
         self._done = torch.empty(n, dtype=torch.uint8, device=dev)
         self._info = torch.empty(n, dtype=torch.uint8, device=dev)
         self._ptr = None
+
+    def _alloc_observations(self, shape):
+        self.observations = torch.zeros(shape, dtype=self.env.obs_dtype, device=self.env.device)
+
+    def nbytes(self):
+        """Bytes of observation storage held on the device."""
+        return self.observations.numel() * self.observations.element_size()
 
     def _stream(self):
         return _lib.raw_stream(self.env.device)
