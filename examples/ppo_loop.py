@@ -25,6 +25,17 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from spacefortress_amd import DeviceRollout, FrameRollout, SFVecEnv, SFVecNormalize  # noqa: E402
+from spacefortress_amd.stats import summarize  # noqa: E402
+
+
+def reward_line(venv, log):
+    """The reward part of the trainer's log line (rl/train.py:158-165) from the device's own bookkeeping: the episode statistics
+    and the episode log's histogram, over the episodes finished so far (stats.py says how that differs from final_rewards)."""
+    s = summarize(venv.episode_stats(), log.histogram(), log.hist_lo)
+    if not s["episodes"]:
+        return "no episode finished yet"
+    return "mean/median reward %.1f/%.1f, min/max reward %.1f/%.1f over %d episodes" % (
+        s["mean_return"], s["median_return"], s["min_return"], s["max_return"], s["episodes"])
 
 
 class ActorCritic(nn.Module):
@@ -107,6 +118,7 @@ def main():
     if a.obs == "image":
         return main_image(a)
     envs = SFVecNormalize(SFVecEnv(a.envs, gametype=a.gametype, spawn_stride=1))
+    log = envs.venv.enable_episode_log()
     ro = DeviceRollout(envs, a.steps)
     net = ActorCritic(envs.venv.obs_dim, envs.venv.n_actions).to(envs.device)
     opt = torch.optim.Adam(net.parameters(), lr=7e-4)
@@ -140,6 +152,7 @@ def main():
             print("iter %3d  env-steps %9d  %.3g env-steps/s (whole loop)  mean final reward %.3f  kills %d" % (
                 it + 1, (it + 1) * a.steps * a.envs, (it + 1) * a.steps * a.envs / dt, float(ro.final_rewards.mean()),
                 ro.num_destruction))
+            print("          " + reward_line(envs.venv, log))
     envs.close()
 
 

@@ -510,6 +510,43 @@ int sf_gather_stacks(const uint8_t* frames_dev, const uint8_t* start_dev, int n_
                      int64_t step, void* out_dev, int out_type, void* stream);
 int sf_gather_errors(uint64_t* count_out, int clear, void* stream);
 
+/* ---- The episode log: one record per finished episode and a histogram of episode returns, kept on the device.  The trainer
+ *      logs mean / median / min / max of the episode returns (rl/train.py:158-165) and the evaluator prints one line per
+ *      finished episode -- return, fortresses destroyed, shots (rl/evaluate.py:82-99); sf_episode_stats holds sums and
+ *      extremes only, so neither a median nor a single episode can come out of it.  A log is a stand-alone object fed with
+ *      the rows a step wrote (plain device pointers; it knows nothing of a batch):
+ *        per env: four int32 running accumulators (return, length, kills, fire actions);
+ *        per log: a ring of `capacity` records of 32 bytes, int64 hist[hist_bins], total (episodes ever logged), rows_seen.
+ *      sf_eplog_update consumes K >= 1 rows of [K][n_envs] arrays -- rew int32, done uint8, info uint8, actions uint8 / int32 /
+ *      int64 (act_type SF_ACT_*) or NULL.  For every env the rows are taken in order k = 0 .. K - 1: return += rew, length += 1,
+ *      kills += info, fire_actions += (action == fire_action) (only with actions); where done[k][e] is set the record
+ *      {e, return, length, kills, fire_actions, end_row = rows_seen + k} is emitted, one count goes to histogram bin
+ *      clamp(return - hist_lo, 0, hist_bins - 1) (the two end bins saturate), and the four accumulators are zeroed.
+ *      ORDER: the records of one update carry the sequence numbers total + r, r = the rank of (k, e) among the set bytes of
+ *      `done` in row-major order k * n_envs + e; sequence number s lives in ring slot s % capacity.  If one update emits more
+ *      than `capacity` records only those with s >= total_after - capacity are written; total counts them all and the
+ *      histogram loses none.  The same inputs give the same ring bytes: the order is a prefix sum, not a race.
+ *      The update is plain stream work on `stream` of the log's device: no allocation, no synchronise, capturable in a HIP
+ *      graph (total and rows_seen advance on the device, so a replay goes on counting).
+ *      sf_eplog_restart zeroes the running accumulators only (the envs start new games otherwise than by `done`);
+ *      sf_eplog_clear the ring, the histogram, total and rows_seen as well.  sf_eplog_read synchronises `stream` and copies
+ *      out total, rows_seen, the ring AS STORED (capacity records; slot s % capacity) and the histogram; any pointer may be
+ *      NULL.  SF_ERR_ARG (with a text): n_envs outside [1, 2^26], capacity outside [1, 2^32], hist_bins outside [1, 65536],
+ *      K < 1, a NULL rew / done / info, an act_type that is none of SF_ACT_*. ---- */
+typedef struct {
+  int32_t env, episode_return, length, kills, fire_actions, reserved;
+  int64_t end_row;
+} sf_episode_record;
+typedef struct sf_eplog sf_eplog;
+int sf_eplog_create(int n_envs, int64_t capacity, int hist_lo, int hist_bins, int fire_action, int device, sf_eplog** out);
+int sf_eplog_destroy(sf_eplog* h);
+int sf_eplog_update(sf_eplog* h, const int32_t* rew_dev, const uint8_t* done_dev, const uint8_t* info_dev,
+                    const void* actions_dev, int act_type, int K, void* stream);
+int sf_eplog_restart(sf_eplog* h, void* stream);
+int sf_eplog_clear(sf_eplog* h, void* stream);
+int sf_eplog_read(sf_eplog* h, uint64_t* total, uint64_t* rows_seen, sf_episode_record* records_host, int64_t* hist_host,
+                  void* stream);
+
 /* ---- host-only helpers (usable without a GPU) ---- */
 typedef struct {
   int32_t width, height, game_time;

@@ -33,6 +33,7 @@ LANE_STATE_MAGIC = 0x53464C00
 LANE_STATE_VERSION = 1
 ACT_I32, ACT_I64 = 4, 8
 STACK_U8, STACK_F16, STACK_F32 = 1, 2, 4  # SF_STACK_* (sfmi.h: sf_gather_stacks)
+EPISODE_RECORD_BYTES = 32  # sizeof(sf_episode_record) (sfmi.h: sf_eplog_read)
 
 
 class SfmiError(RuntimeError):
@@ -136,6 +137,12 @@ SYMBOLS = {
     "sf_gather_stacks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int64,
                                    C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
     "sf_gather_errors": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_void_p]),
+    "sf_eplog_create": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "sf_eplog_destroy": (C.c_int, [C.c_void_p]),
+    "sf_eplog_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "sf_eplog_restart": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "sf_eplog_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "sf_eplog_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_render_stack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sf_render_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "sf_frame_stack_clear": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),

@@ -79,6 +79,26 @@ int sf_step_with_norm_partials(sf_batch* b, const void* actions_dev, int act_typ
                                uint8_t* done_dev, uint8_t* info_dev, double* partials, double* ret, double gamma, int* rows_out,
                                void* stream);
 
+// sf_episode_log.hip: the episode log (sfmi.h: sf_eplog_*).  One update = count, scan, apply over groups of SF_EPLOG_ROWS
+// rows; counts / offs hold SF_EPLOG_ROWS * ceil(n / 256) cells each
+#define SF_EPLOG_ROWS 32
+struct SfEplogHeader {
+  unsigned long long total, rows_seen;  // episodes ever logged, rows ever consumed
+  unsigned long long base_seq, base_row;  // total / rows_seen in front of the group of rows in flight (scan -> apply)
+};
+struct SfEplogArgs {
+  int n, fire_action, bins;
+  long long hist_lo;
+  unsigned long long capacity;
+  int4* acc;  // per env: return, length, kills, fire actions
+  sf_episode_record* ring;
+  unsigned long long* hist;
+  SfEplogHeader* hdr;
+  uint32_t *counts, *offs;
+};
+hipError_t sf_launch_eplog_update(const SfEplogArgs& a, const int32_t* rew, const uint8_t* done, const uint8_t* info,
+                                  const void* actions, int act_type, int K, hipStream_t stream);
+
 // sf_host.cpp (no HIP calls: usable and tested without a GPU)
 void sf_host_fill_consts(const sf_preset& p, double* consts /* SF_CONST_DOUBLES */);
 void sf_set_error(const char* fmt, ...);

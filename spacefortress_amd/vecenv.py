@@ -69,6 +69,7 @@ class SFVecEnv:
                         "spawn_stride": int(spawn_stride), "auto_reset": bool(auto_reset)}
         self.default_geometry = True
         self._durations = None
+        self._episodes = None
         self._fresh = True  # nothing has changed the state sf_create left: a recording may start here
         self._rec = None
         self.num_envs = int(num_envs)
@@ -180,6 +181,8 @@ class SFVecEnv:
         finally:
             self._rollout_events_end(ev)
         self._fresh = False
+        if self._episodes is not None:
+            self._episodes.update(rew, done, info, actions)
         if self._rec is not None:
             self._rec.add(actions.to(torch.uint8), rew, done, info)
         return obs, rew, done, info
@@ -204,20 +207,25 @@ class SFVecEnv:
         wrappers that call the C ABI themselves (FrameStack.step, DeviceRollout.step, SFVecNormalize's fused step): the state is
         no longer the one sf_create left, the duration log appends what the tick pushed (and empties the vectors of an env
         whose episode ended), and a recording gets the actions with the engine's own (unnormalised) reward, done and info of
-        the step(s): [N] or [K, N] device tensors, not synchronised."""
+        the step(s): [N] or [K, N] device tensors, not synchronised.  The episode log (enable_episode_log) follows the same rows."""
         self._fresh = False
         if self._durations is not None:
             self._durations.after(done)
+        if self._episodes is not None:
+            self._episodes.update(rew, done, info, actions)
         if self._rec is not None:
             self._rec.add(actions.to(torch.uint8), rew, done, info)
 
     def _touch(self):
         """The state is about to change otherwise than by a recorded step: a recording cannot go on, and the duration log starts
         over (its vectors belong to the Games the batch held: reset() makes new ones, set_field / load_state_dict put the batch
-        somewhere the log has not followed)."""
+        somewhere the log has not followed).  The episode log drops its running sums -- of EVERY lane, also when only some were
+        loaded (load_lanes / copy_lanes) -- and keeps its finished records and the histogram."""
         self._fresh = False
         if self._durations is not None:
             self._durations.reset()
+        if self._episodes is not None:
+            self._episodes.restart()
         if self._rec is not None:
             self._rec = None
             raise RuntimeError("reset() / set_field() during a recording: a replay file is the game from a NEW batch on; "
@@ -280,7 +288,7 @@ class SFVecEnv:
             bufs = out if out is not None else self._alloc()
             ptrs = tuple(C.c_void_p(t.data_ptr()) for t in bufs)
         ao = None
-        if actions_out is None and self._rec is not None:  # a recording wants to know what was drawn
+        if actions_out is None and (self._rec is not None or self._episodes is not None):  # a recording / the episode log wants to know what was drawn
             actions_out = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
         if actions_out is not None:
             if actions_out.device != self.device or actions_out.dtype != torch.uint8 or not actions_out.is_contiguous() \
@@ -290,6 +298,8 @@ class SFVecEnv:
         self._no_duration_log("step_sampled()")
         _lib.check(self._L.sf_step_sampled(self._h, ao, ptrs[0], ptrs[1], ptrs[2], ptrs[3], self._stream()))
         self._fresh = False
+        if self._episodes is not None:
+            self._episodes.update(bufs[1], bufs[2], bufs[3], actions_out)
         if self._rec is not None:
             self._rec.add(actions_out, bufs[1], bufs[2], bufs[3])
         return bufs
@@ -302,7 +312,7 @@ class SFVecEnv:
         rew = torch.empty((K, n), dtype=torch.int32, device=self.device)
         done = torch.empty((K, n), dtype=torch.uint8, device=self.device)
         info = torch.empty((K, n), dtype=torch.uint8, device=self.device)
-        acts = torch.empty((K, n), dtype=torch.uint8, device=self.device) if (want_actions or self._rec is not None) else None
+        acts = torch.empty((K, n), dtype=torch.uint8, device=self.device) if (want_actions or self._rec is not None or self._episodes is not None) else None
         ev = self._rollout_events_begin(K)
         try:
             _lib.check(self._L.sf_rollout_sampled(self._h, K, C.c_void_p(acts.data_ptr()) if acts is not None else None,
@@ -312,6 +322,8 @@ class SFVecEnv:
         finally:
             self._rollout_events_end(ev)
         self._fresh = False
+        if self._episodes is not None:
+            self._episodes.update(rew, done, info, acts)
         if self._rec is not None:
             self._rec.add(acts, rew, done, info)
         return obs, rew, done, info, acts
@@ -479,6 +491,17 @@ class SFVecEnv:
         from .durations import DurationLog
         self._durations = DurationLog(self, capacity)
         return self._durations
+
+    def enable_episode_log(self, capacity=65536, hist=(-256, 512), fire_action=1):
+        """One record per finished episode (env, return, length, kills, fire actions, the row it ended on) in a ring of `capacity`,
+        and a histogram of the returns (`hist` = (lowest return, bins); the end bins saturate), kept on the device by every
+        stepping path from here on (episodes.py; sfmi.h: sf_eplog_*) -- what the trainer's mean / median / min / max line and the
+        evaluator's per-episode line are made of (rl/train.py:158-165, rl/evaluate.py:82-99).  Returns the log: `log.drain()`,
+        `log.histogram()`, `log.total`.  reset(), set_field() and loaded lanes start the running sums of every lane over;
+        finished records stay.  Off by default: three small launches per step."""
+        from .episodes import EpisodeLog
+        self._episodes = EpisodeLog(self.num_envs, self.device, capacity, hist, fire_action)
+        return self._episodes
 
     def enable_events(self, on=True):
         """Per-tick event bitmasks (sfmi.h SF_EV_*; `_lib.EVENT_NAMES`): after every step `self.events` holds
