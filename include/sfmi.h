@@ -463,10 +463,16 @@ int sf_normalizer_set_state(sf_normalizer* z, const double* host, const double* 
  *      sf_record_step: rl/train.py:82-88 -- reward_out = float(reward), mask_out = 1 - done,
  *      episode_rewards += reward; final_rewards = final_rewards * mask + (1 - mask) * episode_rewards;
  *      episode_rewards *= mask; actions_out (int64, `rollouts.actions[step]`) = the step's actions.
- *      Any output / accumulator may be NULL.
+ *      Any output / accumulator may be NULL.  final_rewards is updated from the step's episode_rewards: with
+ *      episode_rewards NULL it is left as it is (sf_step_record the same).  actions_out widens the caller's values
+ *      (uint8 zero-extended, int32 sign-extended); for an action id outside the action set sf_record_step copies the
+ *      value given, while sf_step_record stores its low 32 bits sign-extended (the two differ only for int64 ids
+ *      beyond int32, which sf_check_actions reports either way).
  *      sf_compute_returns: RolloutStorage.compute_returns (rl/storage.py:50-63) over rewards [T][n],
- *      value_preds [T+1][n] (row T is overwritten with next_value when use_gae, like the reference),
- *      masks [T+1][n], next_value [n] -> returns [T+1][n]; float32, bit-identical to the reference. ---- */
+ *      value_preds [T+1][n] (row T is overwritten with next_value when use_gae, like the reference; without use_gae it is not
+ *      read and may be NULL),
+ *      masks [T+1][n], next_value [n] -> returns [T+1][n] (row T = next_value without use_gae; with use_gae row T
+ *      is not written, as in the reference); float32, bit-identical to the reference. ---- */
 /* sf_step with sf_record_step's bookkeeping in the SAME launch (the epilogue of the step kernel): one launch per
  * trainer step.  reward_f32 is required; mask_f32, episode_rewards, final_rewards, actions_out may be NULL. */
 int sf_step_record(sf_batch* b, const void* actions_dev, int act_type, void* obs_dev, int32_t* reward_dev,
