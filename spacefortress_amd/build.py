@@ -112,8 +112,8 @@ def offload_arch(flags=None):
     return archs[-1] if archs else "gfx950"
 
 
-def device_disassembly(lib=None, arch=None):
-    """The device code objects inside a built libsfmi.so (one per .hip source), disassembled: one string."""
+def device_code_objects(lib=None, arch=None):
+    """The raw device code objects inside a built libsfmi.so: a list of bytes, one per .hip source, in SOURCES' order."""
     import tempfile
 
     lib = lib or LIB
@@ -137,8 +137,25 @@ def device_disassembly(lib=None, arch=None):
             subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o",
                                    "--targets=hipv4-amdgcn-amd-amdhsa--" + arch, "--input=" + part, "--output=" + co],
                                   stderr=subprocess.DEVNULL)
-            out.append(subprocess.check_output([os.path.join(llvm, "llvm-objdump"), "-d", "--mcpu=" + arch, co], text=True))
-    return "\n".join(out)
+            out.append(open(co, "rb").read())
+    return out
+
+
+def disassemble_code_object(co, arch=None):
+    """llvm-objdump -d of one raw code object (bytes)."""
+    import tempfile
+
+    arch = arch or offload_arch()
+    llvm = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "code.co")  # (a fixed name: objdump prints it in its first line)
+        open(path, "wb").write(co)
+        return subprocess.check_output([os.path.join(llvm, "llvm-objdump"), "-d", "--mcpu=" + arch, path], text=True, cwd=td)
+
+
+def device_disassembly(lib=None, arch=None):
+    """The device code objects inside a built libsfmi.so (one per .hip source), disassembled: one string."""
+    return "\n".join(disassemble_code_object(co, arch) for co in device_code_objects(lib, arch))
 
 
 def build(force=False, verbose=False, extra_flags=()):

@@ -751,7 +751,7 @@ extern "C" int sf_draw_records(sf_batch* b, void* host, size_t bytes, int from_s
     sf_set_error("sf_draw_records: this batch has no draw records yet (they come with its first frame)");
     return SF_ERR_ARG;
   }
-  // (the caller gets them env by env, whatever the device layout: sf_drawrec.h SF_DR_LAYOUT)
+  // (the caller gets them env by env, whatever the device layout: sf_drawrec.h)
   std::vector<unsigned char> raw((size_t)b->args.lanes * SF_DR_BYTES);
   HIP_TRY(hipMemcpy(raw.data(), b->d_draw, raw.size(), hipMemcpyDeviceToHost));
   for (long e = 0; e < b->n_envs; e++)  // (a record is contiguous: header, positions, headings)
@@ -821,24 +821,87 @@ extern "C" int sf_reset(sf_batch* b, void* obs_dev, void* stream) {
   return SF_OK;
 }
 
+// One step launch as an entry point asks for it: what sf_step, sf_step_record, sf_rollout, ... differ in.
+struct StepLaunch {
+  const char* who;                // the entry point's name in error texts
+  const void* actions = nullptr;  // the caller's action array, or the batch's sampler records (act_type SF_ACT_SAMPLED)
+  int act_type = SF_ACT_SAMPLED;
+  int n_steps = 1;
+  bool fused = false;  // a rollout: the n_steps ticks in ONE launch (unless an image batch's frames are asked for)
+  int32_t* reward = nullptr;
+  uint8_t* done = nullptr;
+  uint8_t* info = nullptr;
+  // optional patches to the batch's SfKernelArgs
+  float *t_reward = nullptr, *t_mask = nullptr, *t_episode = nullptr, *t_final = nullptr;  // trainer outputs (sf_step_record)
+  int64_t* t_actions = nullptr;
+  uint8_t* act_out = nullptr;  // the sampled actions
+  double *n_partials = nullptr, *n_ret = nullptr;  // the normaliser's partial sums and returns
+  double n_gamma = 0.0;
+};
+
+static int check_act_type(const char* who, int act_type) {
+  if (act_type != SF_ACT_U8 && act_type != SF_ACT_I32 && act_type != SF_ACT_I64) {
+    sf_set_error("%s: act_type must be 1, 4 or 8 (got %d)", who, act_type);
+    return SF_ERR_ARG;
+  }
+  return SF_OK;
+}
+
+// guard -> flush -> launch -> draw_current -> frames: the one path from an entry point to sf_launch_step
+static int launch_steps(sf_batch* b, const StepLaunch& d, void* obs_dev, void* stream) {
+  DeviceGuard guard(b->device);
+  const bool image = is_image(b), sampled = d.act_type == SF_ACT_SAMPLED;
+  SfKernelArgs args = b->args;
+  if (d.t_reward) {
+    args.t_reward = d.t_reward;
+    args.t_mask = d.t_mask;
+    args.t_episode = d.t_episode;
+    args.t_final = d.t_final;
+    args.t_actions = (long long*)d.t_actions;
+  }
+  if (sampled) args.act_out = d.act_out;
+  if (d.n_partials) {
+    args.n_partials = d.n_partials;
+    args.n_ret = d.n_ret;
+    args.n_gamma = d.n_gamma;
+  }
+  const void* actions = sampled ? b->d_actrec : d.actions;
+  SF_FLUSH_VIEW(b, stream);
+  if (!(image && obs_dev)) {
+    HIP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, actions, d.act_type, image ? nullptr : obs_dev, d.reward,
+                           d.done, d.info, d.n_steps, d.fused, (hipStream_t)stream));
+    b->draw_current = b->args.draw != nullptr;  // (an image batch's step launch leaves the draw records of the new state)
+    return SF_OK;
+  }
+  // frames are rendered from the state in HBM, which the fused launch keeps in registers: with frames asked for, the K ticks
+  // go out as K step launches, each followed by its frames -- what K sf_step calls do, in one call.  (Sampled actions: the
+  // tiles' tick counters move on by one per launch, so the actions drawn are the fused launch's.)
+  const size_t n = (size_t)b->n_envs, frame = (size_t)sf_obs_dim(b);
+  for (int t = 0; t < d.n_steps; t++) {
+    const size_t row = (size_t)t * n;  // (a rollout's outputs, event masks included, are [n_steps][n_envs])
+    SfKernelArgs at = args;
+    if (at.act_out) at.act_out += row;
+    if (at.events) at.events += row;
+    HIP_TRY(sf_launch_step(at, b->autoturn, b->preset.shaped != 0,
+                           sampled ? actions : (const unsigned char*)actions + row * (size_t)d.act_type, d.act_type, nullptr,
+                           d.reward ? d.reward + row : nullptr, d.done ? d.done + row : nullptr, d.info ? d.info + row : nullptr,
+                           1, false, (hipStream_t)stream));
+    b->draw_current = b->args.draw != nullptr;
+    const int rc = render(b, b->obs_mode, (uint8_t*)obs_dev + row * frame, 0, (hipStream_t)stream);
+    if (rc != SF_OK) return rc;
+  }
+  return SF_OK;
+}
+
 extern "C" int sf_step(sf_batch* b, const void* actions_dev, int act_type, void* obs_dev, int32_t* reward_dev,
                        uint8_t* done_dev, uint8_t* info_dev, void* stream) {
   if (!b || !actions_dev) {
     sf_set_error("sf_step: null batch or actions");
     return SF_ERR_ARG;
   }
-  if (act_type != SF_ACT_U8 && act_type != SF_ACT_I32 && act_type != SF_ACT_I64) {
-    sf_set_error("sf_step: act_type must be 1, 4 or 8 (got %d)", act_type);
-    return SF_ERR_ARG;
-  }
-  DeviceGuard guard(b->device);
-  const bool image = is_image(b);
-  SF_FLUSH_VIEW(b, stream);
-  HIP_TRY(sf_launch_step(b->args, b->autoturn, b->preset.shaped != 0, actions_dev, act_type, image ? nullptr : obs_dev,
-                         reward_dev, done_dev, info_dev, 1, false, (hipStream_t)stream));
-  b->draw_current = b->args.draw != nullptr;  // (an image batch's step launch leaves the draw records of the new state)
-  if (image && obs_dev) return render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
-  return SF_OK;
+  StepLaunch d{"sf_step", actions_dev, act_type, 1, false, reward_dev, done_dev, info_dev};
+  if (check_act_type(d.who, act_type) != SF_OK) return SF_ERR_ARG;
+  return launch_steps(b, d, obs_dev, stream);
 }
 
 int sf_step_with_norm_partials(sf_batch* b, const void* actions_dev, int act_type, void* obs_dev, int32_t* reward_dev,
@@ -848,23 +911,17 @@ int sf_step_with_norm_partials(sf_batch* b, const void* actions_dev, int act_typ
     sf_set_error("sf_step_normalize: null batch, actions or normalizer");
     return SF_ERR_ARG;
   }
-  if (act_type != SF_ACT_U8 && act_type != SF_ACT_I32 && act_type != SF_ACT_I64) {
-    sf_set_error("sf_step_normalize: act_type must be 1, 4 or 8 (got %d)", act_type);
-    return SF_ERR_ARG;
-  }
+  StepLaunch d{"sf_step_normalize", actions_dev, act_type, 1, false, reward_dev, done_dev, info_dev};
+  if (check_act_type(d.who, act_type) != SF_OK) return SF_ERR_ARG;
   if (is_image(b) || b->args.obs_dim < 4) {
     sf_set_error("sf_step_normalize: VecNormalize applies to 1-D observations (rl/train.py:35)");
     return SF_ERR_ARG;
   }
-  DeviceGuard guard(b->device);
-  SfKernelArgs args = b->args;
-  args.n_partials = partials;
-  args.n_ret = ret;
-  args.n_gamma = gamma;
-  SF_FLUSH_VIEW(b, stream);
-  HIP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, actions_dev, act_type, obs_dev, reward_dev, done_dev,
-                         info_dev, 1, false, (hipStream_t)stream));
-  b->draw_current = b->args.draw != nullptr;  // (an image batch's step launch leaves the draw records of the new state)
+  d.n_partials = partials;
+  d.n_ret = ret;
+  d.n_gamma = gamma;
+  const int rc = launch_steps(b, d, obs_dev, stream);
+  if (rc != SF_OK) return rc;
   *rows_out = (int)(b->args.lanes / 64);
   return SF_OK;
 }
@@ -876,29 +933,19 @@ extern "C" int sf_step_record(sf_batch* b, const void* actions_dev, int act_type
     sf_set_error("sf_step_record: null batch, actions or reward_f32");
     return SF_ERR_ARG;
   }
-  if (act_type != SF_ACT_U8 && act_type != SF_ACT_I32 && act_type != SF_ACT_I64) {
-    sf_set_error("sf_step_record: act_type must be 1, 4 or 8 (got %d)", act_type);
-    return SF_ERR_ARG;
-  }
+  StepLaunch d{"sf_step_record", actions_dev, act_type, 1, false, reward_dev, done_dev, info_dev};
+  if (check_act_type(d.who, act_type) != SF_OK) return SF_ERR_ARG;
   if (((uintptr_t)reward_f32 | (uintptr_t)mask_f32 | (uintptr_t)episode_rewards | (uintptr_t)final_rewards) & 3 ||
       ((uintptr_t)actions_out & 7)) {
     sf_set_error("sf_step_record: float outputs must be 4-byte, actions_out 8-byte aligned");
     return SF_ERR_ARG;
   }
-  DeviceGuard guard(b->device);
-  SfKernelArgs args = b->args;
-  args.t_reward = reward_f32;
-  args.t_mask = mask_f32;
-  args.t_episode = episode_rewards;
-  args.t_final = final_rewards;
-  args.t_actions = (long long*)actions_out;
-  const bool image = is_image(b);
-  SF_FLUSH_VIEW(b, stream);
-  HIP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, actions_dev, act_type, image ? nullptr : obs_dev,
-                         reward_dev, done_dev, info_dev, 1, false, (hipStream_t)stream));
-  b->draw_current = b->args.draw != nullptr;  // (an image batch's step launch leaves the draw records of the new state)
-  if (image && obs_dev) return render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
-  return SF_OK;
+  d.t_reward = reward_f32;  // (never null here: it is what switches the trainer outputs on)
+  d.t_mask = mask_f32;
+  d.t_episode = episode_rewards;
+  d.t_final = final_rewards;
+  d.t_actions = actions_out;
+  return launch_steps(b, d, obs_dev, stream);
 }
 
 extern "C" int sf_rollout(sf_batch* b, const void* actions_dev, int act_type, int n_steps, void* obs_dev,
@@ -907,37 +954,13 @@ extern "C" int sf_rollout(sf_batch* b, const void* actions_dev, int act_type, in
     sf_set_error("sf_rollout: null batch or actions");
     return SF_ERR_ARG;
   }
-  if (act_type != SF_ACT_U8 && act_type != SF_ACT_I32 && act_type != SF_ACT_I64) {
-    sf_set_error("sf_rollout: act_type must be 1, 4 or 8 (got %d)", act_type);
-    return SF_ERR_ARG;
-  }
+  StepLaunch d{"sf_rollout", actions_dev, act_type, n_steps, true, reward_dev, done_dev, info_dev};
+  if (check_act_type(d.who, act_type) != SF_OK) return SF_ERR_ARG;
   if (n_steps <= 0 || (double)n_steps * b->n_envs * 8.0 >= 4294967296.0) {
     sf_set_error("sf_rollout: n_steps must be positive and n_steps * n_envs * 8 < 2^32 (got %d)", n_steps);
     return SF_ERR_ARG;
   }
-  DeviceGuard guard(b->device);
-  SF_FLUSH_VIEW(b, stream);
-  if (is_image(b) && obs_dev) {
-    // frames are rendered from the state in HBM, which the fused launch keeps in registers: with frames asked for, the K ticks
-    // go out as K step launches, each followed by its frames -- what K sf_step calls do, in one call
-    const size_t n = (size_t)b->n_envs, frame = (size_t)sf_obs_dim(b);
-    for (int t = 0; t < n_steps; t++) {
-      const size_t row = (size_t)t * n;
-      SfKernelArgs args = b->args;
-      if (args.events) args.events += row;  // (a rollout's event masks are [n_steps][n_envs], like its other outputs)
-      HIP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, (const unsigned char*)actions_dev + row * (size_t)act_type,
-                             act_type, nullptr, reward_dev ? reward_dev + row : nullptr, done_dev ? done_dev + row : nullptr,
-                             info_dev ? info_dev + row : nullptr, 1, false, (hipStream_t)stream));
-      b->draw_current = b->args.draw != nullptr;
-      const int rc = render(b, b->obs_mode, (uint8_t*)obs_dev + row * frame, 0, (hipStream_t)stream);
-      if (rc != SF_OK) return rc;
-    }
-    return SF_OK;
-  }
-  HIP_TRY(sf_launch_step(b->args, b->autoturn, b->preset.shaped != 0, actions_dev, act_type, obs_dev, reward_dev, done_dev, info_dev,
-                         n_steps, true, (hipStream_t)stream));
-  b->draw_current = b->args.draw != nullptr;  // (an image batch's step launch leaves the draw records of the new state)
-  return SF_OK;
+  return launch_steps(b, d, obs_dev, stream);
 }
 
 extern "C" int sf_seed_actions(sf_batch* b, uint64_t seed, uint32_t first_lane, void* stream) {
@@ -955,16 +978,9 @@ extern "C" int sf_step_sampled(sf_batch* b, uint8_t* actions_out_dev, void* obs_
     sf_set_error("sf_step_sampled: null batch");
     return SF_ERR_ARG;
   }
-  DeviceGuard guard(b->device);
-  const bool image = is_image(b);
-  SfKernelArgs args = b->args;
-  args.act_out = actions_out_dev;
-  SF_FLUSH_VIEW(b, stream);
-  HIP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, b->d_actrec, SF_ACT_SAMPLED, image ? nullptr : obs_dev,
-                         reward_dev, done_dev, info_dev, 1, false, (hipStream_t)stream));
-  b->draw_current = b->args.draw != nullptr;  // (an image batch's step launch leaves the draw records of the new state)
-  if (image && obs_dev) return render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
-  return SF_OK;
+  StepLaunch d{"sf_step_sampled", nullptr, SF_ACT_SAMPLED, 1, false, reward_dev, done_dev, info_dev};
+  d.act_out = actions_out_dev;
+  return launch_steps(b, d, obs_dev, stream);
 }
 
 extern "C" int sf_rollout_sampled(sf_batch* b, int n_steps, uint8_t* actions_out_dev, void* obs_dev, int32_t* reward_dev,
@@ -977,32 +993,9 @@ extern "C" int sf_rollout_sampled(sf_batch* b, int n_steps, uint8_t* actions_out
     sf_set_error("sf_rollout_sampled: n_steps must be positive and n_steps * n_envs < 2^32 (got %d)", n_steps);
     return SF_ERR_ARG;
   }
-  DeviceGuard guard(b->device);
-  SfKernelArgs args = b->args;
-  args.act_out = actions_out_dev;
-  SF_FLUSH_VIEW(b, stream);
-  if (is_image(b) && obs_dev) {
-    // with frames: n_steps sampled step launches, each followed by its frames (sf_rollout does the same); the tiles' tick
-    // counters move on by one per launch, so the actions drawn are the fused launch's
-    const size_t n = (size_t)b->n_envs, frame = (size_t)sf_obs_dim(b);
-    for (int t = 0; t < n_steps; t++) {
-      const size_t row = (size_t)t * n;
-      SfKernelArgs at = b->args;
-      at.act_out = actions_out_dev ? actions_out_dev + row : nullptr;
-      if (at.events) at.events += row;
-      HIP_TRY(sf_launch_step(at, b->autoturn, b->preset.shaped != 0, b->d_actrec, SF_ACT_SAMPLED, nullptr,
-                             reward_dev ? reward_dev + row : nullptr, done_dev ? done_dev + row : nullptr,
-                             info_dev ? info_dev + row : nullptr, 1, false, (hipStream_t)stream));
-      b->draw_current = b->args.draw != nullptr;
-      const int rc = render(b, b->obs_mode, (uint8_t*)obs_dev + row * frame, 0, (hipStream_t)stream);
-      if (rc != SF_OK) return rc;
-    }
-    return SF_OK;
-  }
-  HIP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, b->d_actrec, SF_ACT_SAMPLED, obs_dev, reward_dev, done_dev,
-                         info_dev, n_steps, true, (hipStream_t)stream));
-  b->draw_current = b->args.draw != nullptr;  // (an image batch's step launch leaves the draw records of the new state)
-  return SF_OK;
+  StepLaunch d{"sf_rollout_sampled", nullptr, SF_ACT_SAMPLED, n_steps, true, reward_dev, done_dev, info_dev};
+  d.act_out = actions_out_dev;
+  return launch_steps(b, d, obs_dev, stream);
 }
 
 extern "C" int sf_check_state(sf_batch* b, void* stream) {

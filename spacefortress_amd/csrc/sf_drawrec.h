@@ -37,33 +37,19 @@
 #define SF_DR_BYTES (SF_DR_ANGLES_OFF + 48) /* 432 */
 // In HBM the records of a wave tile (64 envs, sf_layout.h) form one block of SF_DR_TILE_BYTES; env lane l's 16-byte piece p
 // (pieces 0, 1 = header words 0..3, 4..7; piece 2 + k = object k's transform) sits at l * SF_DR_LANE_STRIDE + p *
-// SF_DR_PIECE_STRIDE.  SF_DR_LAYOUT 0: env by env (384 contiguous bytes per env).  The frame kernel is a wave per env: its
+// SF_DR_PIECE_STRIDE.  Env by env (384 contiguous bytes per env): the frame kernel is a wave per env, and its
 // two scalar loads and its lanes' transform loads then touch three or four 128-byte lines, 0.5 KB per frame.
-// SF_DR_LAYOUT 1: rows of 64 x 16 bytes like the state's chunks -- every store of the step kernel (a lane per env) a
+// (Rows of 64 x 16 bytes like the state's chunks would make every store of the step kernel -- a lane per env -- a
 // coalesced 1 KiB row, but a frame then pulls up to 23 different lines, 2.9 KB: measured 45.5 against 42.9 us per 16 384
-// frames, for 0 us on the step kernel (profiles/r04_render_versions.md).
-#ifndef SF_DR_LAYOUT
-#define SF_DR_LAYOUT 0
-#endif
+// frames, for 0 us on the step kernel, profiles/r04_render_versions.md.)
 #define SF_DR_PIECES (2 + SF_DR_OBJS)
 #define SF_DR_TILE_BYTES (64 * SF_DR_BYTES)
-#if SF_DR_LAYOUT != 0
-#error "the rows-of-64 layout of round 4's A/B is gone: the headings' array has no place in it"
-#endif
-#if SF_DR_LAYOUT == 0
 #define SF_DR_LANE_STRIDE SF_DR_BYTES
 #define SF_DR_PIECE_STRIDE 16
-#else
-#define SF_DR_LANE_STRIDE 16
-#define SF_DR_PIECE_STRIDE 1024
-#endif
 #define SF_DR_PIECE_OBJ0 2
-// the cache bits of the step kernel's record stores (aux of the buffer-store builtins): 0 = plain -- the header's two pieces
-// and the ship's and the fortress's transforms are 64 contiguous bytes per env and merge in L2; 16 = sc1, write-through
-// like the state's chunks: each piece then leaves as a partial line of its own (step launch 8.45 against 7.74 us)
-#ifndef SF_DR_AUX
-#define SF_DR_AUX 0
-#endif
+// The step kernel's record stores are plain (aux 0 of the buffer-store builtins): the header's two pieces and the ship's
+// and the fortress's transforms are 64 contiguous bytes per env and merge in L2; write-through (sc1) like the state's
+// chunks, each piece leaves as a partial line of its own (step launch 8.45 against 7.74 us)
 
 // header words
 #define SF_DRW_SHIP_X 0  /* (float)ship_x, bits */

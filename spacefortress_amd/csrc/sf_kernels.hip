@@ -22,7 +22,7 @@
 //    kernel is a latency chain, not a throughput problem.  It is organised so that a
 //    wave makes two memory round trips, not twenty: (1) every unconditional load is
 //    issued up front; (2) as soon as the two alive-bitmasks arrive, the live
-//    projectile slots are prefetched -- a wave ballot skips slot groups no lane uses --
+//    projectile slots are prefetched -- a wave ballot skips slots no lane uses --
 //    and their latency hides under the key / ship / fortress arithmetic;
 //  * projectile ballistics run as straight-line code over the prefetched slots (the
 //    slots are independent until a hit), so their f64 chains interleave; only the
@@ -55,28 +55,32 @@
 #include "sf_deg_dd.h"
 #include "sf_drawrec.h"
 
+// ---- the build's switches: numeric tunables that name a real quantity, and one instrument (SF_STAMPS) ----
 // Four waves per workgroup share one LDS copy of the cos/sin table (one barrier, early, while the
 // waves are still in step; a copy per wave was tried: 1024 waves pulling the same 45 cache lines
 // out of L2 at once made the load phase 3x longer).  Everything after that is wave-private.
 #ifndef SF_BLOCK
 #define SF_BLOCK 256
 #endif
+#ifndef SF_SPLIT
+#define SF_SPLIT 1 /* 1: batches up to 65 536 envs (at most one games' wave per SIMD) step by split launches (sf_step_kernel, BLKP = 1000 + BLK): A/B 4 096 envs 5.48 -> 5.29 us, 32 768: 6.11 -> 5.89, 65 536: 6.51 -> 6.39; 0: never; 2: every batch the instantiation can serve (tests) */
+#endif
+#ifndef SF_MROWS
+#define SF_MROWS 3 /* rows of the tile's missile pool (64 entries each) loaded up front with the lane's chunks; more live
+                      missiles than that (> 192 in 64 envs; random play averages 104) take the dependent-load loop */
+#endif
+#ifndef SF_SPF
+#define SF_SPF 6 /* shell slots prefetched, one at a time (A/B at 65 536 envs with the missile pool: pairs 6.82 us per launch, singles 6.75) */
+#endif
+#ifndef SF_STAGGER
+#define SF_STAGGER 12 /* x 64 cycles (sf_step_kernel's staggered start); A/B at 65 536 envs: 0: 7.02 us per launch, 8: 6.84, 16: 6.84, 24: 6.89, 40: 7.36 */
+#endif
+
 // LDS map (doubles): [0, SF_LDS_DOUBLES) the cos/sin table; then one (hit, out) pair of 32-bit event words per lane,
 // through which the missile pool's entries tell their owner lanes what happened to them; then the observation staging
 #define SF_LDS_EV SF_LDS_DOUBLES
 /* then (sf_step_kernel: kLdsAtab, kLdsStage) behind the BLK event words: atan(k / 16), k = 0..16 (sf_atan2_core), and the staging rows */
 #define SF_MAX_MISSILES_D 20.0 /* sf.MAX_MISSILES / sf.MAX_SHELLS as divisors (ENV:124-125) */
-#ifndef SF_MROWS
-#ifndef SF_SPLIT
-#define SF_SPLIT 1 /* 1: batches up to 65 536 envs (at most one games' wave per SIMD) step by split launches (sf_step_kernel, BLKP = 1000 + BLK): A/B 4 096 envs 5.48 -> 5.29 us, 32 768: 6.11 -> 5.89, 65 536: 6.51 -> 6.39; 0: never; 2: every batch the instantiation can serve (tests) */
-#endif
-#define SF_MROWS 3 /* rows of the tile's missile pool (64 entries each) loaded up front with the lane's chunks; more live
-                      missiles than that (> 192 in 64 envs; random play averages 104) take the dependent-load loop */
-#endif
-#define SF_SPF 6 /* shell slots prefetched (groups of SF_SGSZ) */
-#ifndef SF_SGSZ
-#define SF_SGSZ 1 /* A/B at 65 536 envs with the missile pool: pairs 6.82 us per launch, singles 6.75 */
-#endif
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -104,66 +108,17 @@
   (tb + sfl::chunk_offset(SF_G_##group, 0) +                 \
    (size_t)(s) * (size_t)(sfl::kGroups[SF_G_##group].chunk * sfl::kTileLanes))
 #define SF_LD(T, base, off) (*reinterpret_cast<const T*>((base) + (off)))
-// SF_STORE_MODE (A/B switch, tools/ab.py on one device, 65 536 envs): 0 plain stores 11.20 us per
-// launch, 1 non-temporal 11.01, 2 write-through (`sc1`) for the 16-byte chunks 10.83 -- the bytes
-// leave L2 while the kernel still runs, so the end-of-kernel write-back has less to flush.  (With
-// the earlier 1-8-byte rows `sc1` LOST 1 %: narrow write-through stores are one fabric write each.)
-// Nothing stored this way is read again inside the launch.
-#ifndef SF_OBS_NT
-#define SF_OBS_NT 0
-#endif
-// SF_ABL_TRIG (timing-only ablation, results are WRONG when set): 1 = no workgroup barrier after the
-// table staging, 2 = no table at all (hardware v_cos_f32 / v_sin_f32 instead of the exact entries).
-#ifndef SF_ABL_TRIG
-#define SF_ABL_TRIG 0
-#endif
-#ifndef SF_AXIS_VEL
-#define SF_AXIS_VEL 0 /* 1: the near-axis form of sf_atan2 for the velocity bearing as well.  It only feeds the `vdir`
-                         observation, a velocity component within 2^-27 of zero takes an exact cancellation of thrusts that
-                         the 0.3 * cos / sin(6k degrees) steps do not produce, and the test costs 0.1 us per launch */
-#endif
-#ifndef SF_OBS_SC1
-#define SF_OBS_SC1 1 /* the observation rows leave write-through (`sc1`) like the state chunks: 5 MB less for the
-                        end-of-kernel write-back, 8.19 -> 7.94 us per launch; the 4- and 1-byte outputs gain nothing */
-#endif
-#ifndef SF_ABL_STATS
-#define SF_ABL_STATS 0
-#endif
-#ifndef SF_ABL_SPAWN
-#define SF_ABL_SPAWN 0
-#endif
-// SF_ABL_PROJ (timing-only ablation, results are WRONG when set): 1 = no missile prefetch / ballistics, 2 = no shells
-// either, 3 = only the shells removed.  SF_ABL_OBS: 1 = no observation epilogue.  SF_ABL_ATAN: 1 = no velocity bearing,
-// 2 = neither bearing (cheap stand-ins).
-#ifndef SF_ABL_PROJ
-#define SF_ABL_PROJ 0
-#endif
-#ifndef SF_ABL_OBS
-#define SF_ABL_OBS 0
-#endif
-#ifndef SF_ABL_ATAN
-#define SF_ABL_ATAN 0
-#endif
-#if SF_ABL_TRIG == 2
-#define SF_COS(ang) ((double)__builtin_amdgcn_cosf((float)(ang) * (1.0f / 360.0f)))
-#define SF_SIN(ang) ((double)__builtin_amdgcn_sinf((float)(ang) * (1.0f / 360.0f)))
-#else
 #define SF_COS(ang) trig[2 * (ang)]
 #define SF_SIN(ang) trig[2 * (ang) + 1]
-#endif
-#ifndef SF_STORE_MODE
-#define SF_STORE_MODE 2
-#endif
+// Stores of 16-byte chunks are write-through (`sc1`): the bytes leave L2 while the kernel still runs, so the
+// end-of-kernel write-back has less to flush (A/B, tools/ab.py on one device, 65 536 envs: plain stores 11.20 us per
+// launch, non-temporal 11.01, write-through 10.83.  With the earlier 1-8-byte rows `sc1` LOST 1 %: narrow
+// write-through stores are one fabric write each).  Nothing stored this way is read again inside the launch.
 // the cache bits of the write-through stores: inline-asm text and the builtins' aux value (1 = sc0, 2 = nt, 16 = sc1)
-#ifndef SF_SC_AUX
 #define SF_SC_AUX 16
 #define SF_SC_ASM "sc1"
-#endif
 template <typename T>
 __device__ __forceinline__ void sf_store(T* p, T v) {
-#if SF_STORE_MODE == 1
-  __builtin_nontemporal_store(v, p);
-#elif SF_STORE_MODE == 2
   if constexpr (sizeof(T) == 16) {
     // the s_nop belongs to the store: a store of more than 64 bits reads its data registers over several cycles and
     // the next VALU write of one of them needs a wait state in between, which the compiler cannot insert for an
@@ -172,9 +127,6 @@ __device__ __forceinline__ void sf_store(T* p, T v) {
   } else {
     *p = v;
   }
-#else
-  *p = v;
-#endif
 }
 #define SF_ST(T, base, off, v) sf_store<T>(reinterpret_cast<T*>((base) + (off)), (T)(v))
 
@@ -314,13 +266,10 @@ __device__ __forceinline__ double sf_atan2_core(double y, double x, const double
   a = x < 0 ? 3.141592653589793 - a : a;
   return copysign(a, y);
 }
-#ifndef SF_FAST_ATAN
-#define SF_FAST_ATAN 1 /* 0: the device libm's atan2 everywhere (A/B) */
-#endif
 
 template <bool RAZOR>
 __device__ __forceinline__ double sf_atan2(double y, double x, const double* atab = nullptr) {
-  double r = (SF_FAST_ATAN && atab) ? sf_atan2_core(y, x, atab) : atan2(y, x);
+  double r = atab ? sf_atan2_core(y, x, atab) : atan2(y, x);
   const double ax = fabs(x), ay = fabs(y);
   const bool ny = ax * 0x1p27 < ay;              // next to the y axis (x == 0 included)
   const bool nx = (x < 0) & (ay * 0x1p27 < ax);  // next to the negative x axis (y == 0 included)
@@ -529,7 +478,7 @@ __device__ __forceinline__ void unpack_lane_late(const LaneLate& t, Lane& L) {
 // The lane's seven chunks back to the tile, through the wave's descriptor: the chunk offsets ride in the scalar
 // offset, no 64-bit address per store; write-through (SF_SC_AUX).
 __device__ __forceinline__ void store_lane_buf(__amdgpu_buffer_rsrc_t rs, const Off& o, const Lane& L) {
-  constexpr int aux = SF_STORE_MODE == 2 ? SF_SC_AUX : 0;
+  constexpr int aux = SF_SC_AUX;
 #define SF_BST16(group, v) \
   sf_buf_st128<aux>(__builtin_bit_cast(u4_t, v), rs, o.o16, SF_GOFF(group, 0))
   SF_BST16(ship_pos, (d2_t{L.sx, L.sy}));
@@ -734,12 +683,8 @@ __device__ __forceinline__ void flush_features_f32(const float* stage_w, float* 
     if (k * 64 + 63 < NV || (int)lane + k * 64 < NV) v[k] = reinterpret_cast<const f4_t*>(stage_w)[lane + k * 64];
 #pragma unroll
   for (int k = 0; k < IT; k++)
-    if (SF_ABL_OBS != 2 && (k * 64 + 63 < NV || (int)lane + k * 64 < NV)) {  // SF_ABL_OBS 2 (timing-only): no global stores
-#if SF_OBS_SC1
+    if (k * 64 + 63 < NV || (int)lane + k * 64 < NV) {
       sf_store<f4_t>(reinterpret_cast<f4_t*>(dst_w) + lane + k * 64, v[k]);  // write-through, like the state chunks
-#else
-      reinterpret_cast<f4_t*>(dst_w)[lane + k * 64] = v[k];
-#endif
     }
 }
 
@@ -765,13 +710,7 @@ __device__ __forceinline__ void flush_obs_wave(const SfKernelArgs& a, const T* s
     typedef T vec_t __attribute__((ext_vector_type(V)));
     const int nvec = total / V;
     for (int v = lane; v < nvec; v += 64) {
-#if SF_OBS_NT
-      __builtin_nontemporal_store(reinterpret_cast<const vec_t*>(stage_w)[v], reinterpret_cast<vec_t*>(dst) + v);
-#elif SF_OBS_SC1
       sf_store<vec_t>(reinterpret_cast<vec_t*>(dst) + v, reinterpret_cast<const vec_t*>(stage_w)[v]);
-#else
-      reinterpret_cast<vec_t*>(dst)[v] = reinterpret_cast<const vec_t*>(stage_w)[v];
-#endif
     }
     done_elems = nvec * V;
   }
@@ -909,7 +848,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   const bool real = i < (unsigned)n_envs_p;  // lanes in [n_envs, lanes) are padding: they run NOOPs
   // predicated access to one projectile slot of the lane: `goff` = SF_GOFF(group, slot), wave-uniform
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(tb, 0, (int)sfl::kTileBytes, 0x00020000);
-  constexpr int kStAux = SF_STORE_MODE == 2 ? SF_SC_AUX : 0;
+  constexpr int kStAux = SF_SC_AUX;
   auto pld16 = [&](unsigned goff, bool p) __attribute__((always_inline)) -> d2_t {
     return __builtin_bit_cast(d2_t, __builtin_amdgcn_raw_buffer_load_b128(rs, p ? o.o16 : SF_OOB, goff, 0));
   };
@@ -926,27 +865,12 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
 #endif
   SF_STAMP(0, false);
 
-#ifndef SF_STAGGER
-#define SF_STAGGER 12 /* x 64 cycles; A/B at 65 536 envs: 0: 7.02 us per launch, 8: 6.84, 16: 6.84, 24: 6.89, 40: 7.36 */
-#endif
 #if SF_STAGGER
   // Half of the workgroups (every other one of an XCD's: workgroup i runs on XCD i % 8) start a third of a microsecond
   // late: a launch is a chip-wide load burst, then arithmetic with the fabric idle, then a store burst; staggered, one
   // half's bursts meet the other half's arithmetic.
   // (a batch that leaves CUs idle has no burst to split; the batch size is a preloaded kernel argument, gridDim is a load)
-#ifndef SF_STAGGER_PHASES
-#define SF_STAGGER_PHASES 2 /* A/B (tools/ab.py, round 4): 3 or 4 phases of SF_STAGGER x 64 cycles each, see NOTES.md */
-#endif
-#if SF_STAGGER_PHASES == 2
   if (n_envs_p > 65536 - 256 && ((blockIdx.x >> 3) & 1u)) __builtin_amdgcn_s_sleep(SF_STAGGER);
-#else
-  if (n_envs_p > 65536 - 256) {
-    const unsigned ph = (blockIdx.x >> 3) % SF_STAGGER_PHASES;  // uniform
-    if (ph == 1) __builtin_amdgcn_s_sleep(SF_STAGGER);
-    if (ph == 2) __builtin_amdgcn_s_sleep(2 * SF_STAGGER);
-    if (ph == 3) __builtin_amdgcn_s_sleep(3 * SF_STAGGER);
-  }
-#endif
 #endif
   // A poll of a hand-over word gives up after 2^18 rounds of 64+ cycles (10 ms; a launch lasts 6 us): a kernel must end
   // whatever happens to the other wave.  Giving up is counted (SF_ACC_HANDOVER -> sf_check_state fails: the step is wrong).
@@ -968,14 +892,8 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     // here: -0.12): in its arithmetic the first wave keeps the SIMD's one VALU busy most of the time, and the second wave's
     // instructions take the same issue slots.  Issue priority for the first wave and a later start for the pool's loads
     // changed nothing measurable; starting them 1 500 cycles later made the games wait; asked for without waiting for the
-    // pool's count (SF_SPLIT_UNCOND): nothing either (tools/ab.py, NOTES.md, profiles/r04_split_ab.txt).
+    // pool's count: nothing either (tools/ab.py, NOTES.md, profiles/r04_split_ab.txt, profiles/closed_switches.md).
     if (tid_all >= (unsigned)BLK) {  // wave-uniform
-#ifndef SF_SPLIT_PPRIO
-#define SF_SPLIT_PPRIO 0 /* A/B: the missile wave at this issue priority (s_setprio): the tiles with the fullest pools are the launch's last */
-#endif
-#if SF_SPLIT_PPRIO
-      __builtin_amdgcn_s_setprio(SF_SPLIT_PPRIO);
-#endif
       // the pool's count rides in every lane's misc chunk: lane 0's word, by a scalar load
       const unsigned n_word = *reinterpret_cast<const __attribute__((address_space(4))) unsigned*>(
           reinterpret_cast<const __attribute__((address_space(4))) void*>(
@@ -990,31 +908,15 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
       const unsigned m_live = n_word >> SF_MPOOL_SHIFT;
       d2_t prow[SF_MROWS];
       unsigned pmeta[SF_MROWS];
-#ifndef SF_SPLIT_LATE
-#define SF_SPLIT_LATE 1 /* the pool's rows are asked for once the table piece is in, i.e. behind the launch's first burst */
-#endif
-#if SF_SPLIT_LATE
 #pragma unroll
       for (int k = 0; k < kTrigPieces; k++) reinterpret_cast<d2_t*>(lds)[cpi0[k]] = cst0[k];
       if (lane < 4u) hflags[lane] = 0u;
-#if SF_SPLIT_LATE > 1
-      __builtin_amdgcn_s_sleep(SF_SPLIT_LATE);
-#endif
-#endif
 #pragma unroll
       for (int r = 0; r < SF_MROWS; r++) {
-#ifndef SF_SPLIT_UNCOND
-#define SF_SPLIT_UNCOND 0 /* A/B: the rows asked for whatever the pool's count is (no wait for the count in front of them) */
-#endif
-        const bool in_ = SF_SPLIT_UNCOND || 64u * r + lane < m_live;
+        const bool in_ = 64u * r + lane < m_live;
         prow[r] = __builtin_bit_cast(d2_t, __builtin_amdgcn_raw_buffer_load_b128(rs, in_ ? o.o16 : SF_OOB, SF_GOFF(missile_pos, r), 0));
         pmeta[r] = __builtin_amdgcn_raw_buffer_load_b32(rs, in_ ? o.o4 : SF_OOB, SF_GOFF(missile_meta, r), 0);
       }
-#if !SF_SPLIT_LATE
-#pragma unroll
-      for (int k = 0; k < kTrigPieces; k++) reinterpret_cast<d2_t*>(lds)[cpi0[k]] = cst0[k];
-      if (lane < 4u) hflags[lane] = 0u;
-#endif
       __syncthreads();  // (the workgroup's one barrier: the cos/sin table is in LDS, the hand-over words are zero)
       const double* trig = lds;
       d2_t pcs[SF_MROWS];
@@ -1071,12 +973,6 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
       return;
     }
   }
-#ifndef SF_SPLIT_PRIO
-#define SF_SPLIT_PRIO 0 /* A/B: the games' wave at this issue priority over its missile wave (s_setprio) */
-#endif
-#if SF_SPLIT_PRIO
-  if constexpr (SPLIT) __builtin_amdgcn_s_setprio(SF_SPLIT_PRIO);
-#endif
   // ================= round trip 1: every unconditional load =================
   // act_type SF_ACT_SAMPLED: no action array -- `actions` is this batch's sampler records (SfActRec, one per tile) and the
   // lane draws its action itself: Philox4x32-10 keyed by the seed, counter (lane of the whole job, tick).  The record is
@@ -1122,25 +1018,18 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   // (behind the last load of the early set: the ten rounds run while those are in flight)
   int act_sampled = 0;
   if (XTRA && act_type == SF_ACT_SAMPLED) act_sampled = sample_action(0);  // uniform branch, VALU only
-  // lane l takes entry 64 r + l if the pool has that many (`n_pool`: the tile's count, known once the early set is in;
-  // ~0u = not known yet, take everything): the instructions are unconditional, the bytes are not
+  // lane l takes entry 64 r + l if the pool has that many (`n_pool`: the tile's count, known once the early set is in):
+  // the instructions are unconditional, the bytes are not
 #define SF_LOAD_POOL_ROWS(aux, n_pool)                                                                                        \
   _Pragma("unroll") for (int r = 0; r < SF_MROWS; r++) {                                                                      \
     const bool in_ = 64u * r + lane < (n_pool);                                                                               \
     prow[r] = __builtin_bit_cast(d2_t, __builtin_amdgcn_raw_buffer_load_b128(rs, in_ ? o.o16 : SF_OOB, SF_GOFF(missile_pos, r), (aux)));   \
     pmeta[r] = __builtin_amdgcn_raw_buffer_load_b32(rs, in_ ? o.o4 : SF_OOB, SF_GOFF(missile_meta, r), (aux));               \
   }
-  constexpr bool kPoolLoads = !SPLIT && (SF_ABL_PROJ == 0 || SF_ABL_PROJ == 3);
+  constexpr bool kPoolLoads = !SPLIT;
   d2_t prow[SF_MROWS];
   unsigned pmeta[SF_MROWS];
   LaneLate late;
-#ifndef SF_LATE
-#define SF_LATE 1 /* 0: the late set rides with the early one (A/B) */
-#endif
-#if !SF_LATE
-  late = load_lane_late(tb, o);
-  if (kPoolLoads) { SF_LOAD_POOL_ROWS(0, ~0u) }
-#endif
   SF_STAMP(1, false);
   SF_STAMP(2, true);
 
@@ -1151,10 +1040,8 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   // For the same reason EVERY load issued so far is waited for here, explicitly (vmcnt(0), the other counters
   // untouched): a first use of, say, the flags after the predicated loads would otherwise be a vmcnt(0) too.
   __builtin_amdgcn_s_waitcnt(0x0F70);
-#if SF_ABL_TRIG != 2
 #pragma unroll
   for (int k = 0; k < kTrigPieces; k++) reinterpret_cast<d2_t*>(lds)[cpi[k]] = cst[k];
-#endif
   // this lane's (hit, out) event words start at zero; the missile pool's entries OR their slot bit into their
   // OWNER's words (wave-private: only lanes of this wave own entries of this tile; LDS is in order per wave)
   unsigned long long* const evw = reinterpret_cast<unsigned long long*>(lds + SF_LDS_EV) + (tid & ~63u);
@@ -1162,16 +1049,13 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   reinterpret_cast<d2_t*>(lds + kLdsAtab)[atab_pi] = atab_piece;  // (every lane the same nine pieces: no branch)
 
   // ================= round trip 2: live shell slots, predicated by the alive mask ======
-  // Slot groups (pairs): a wave ballot skips a group no lane uses.  The kernel lasts as long as its slowest wave, so
-  // the groups reach well past the common case: the dependent-load loop behind them is for slots hardly ever used.
+  // Slot by slot: a wave ballot skips a slot no lane uses.  The kernel lasts as long as its slowest wave, so
+  // the slots reach well past the common case: the dependent-load loop behind them is for slots hardly ever used.
   // (Missiles need no second round trip: the tile's pool rows came with the first.)
   double shx[SF_SPF], shy[SF_SPF], shvx[SF_SPF], shvy[SF_SPF];
-#ifndef SF_SHELL_INIT
-#define SF_SHELL_INIT 0
-#endif
 #pragma unroll
   for (int s = 0; s < SF_SPF; s++) {
-    if (FUSED || SF_SHELL_INIT) {
+    if (FUSED) {
       shx[s] = shy[s] = shvx[s] = shvy[s] = 0;
     } else {
       // one tick per launch: a slot's registers are read only under the same wave-wide test that loaded them, and what a
@@ -1188,21 +1072,20 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   const __amdgpu_buffer_rsrc_t rs_spawn =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<int16_t*>(a.spawn), 0, (int)((a.spawn_mask + 1u) * 8u), 0x00020000);
   auto load_spawn = [&]() __attribute__((always_inline)) {
-#if SF_ABL_SPAWN  /* timing-only: no dependent spawn-entry load (WRONG results) */
-    spawn_e = 0x0000005A00C800C8ull + (L.cursor & 63u);
-#else
     const i2_t e = __builtin_bit_cast(i2_t, __builtin_amdgcn_raw_buffer_load_b64(rs_spawn, will_respawn ? (L.cursor & a.spawn_mask) * 8u : SF_OOB, 0, 0));
     spawn_e = (unsigned long long)(unsigned)e.x | ((unsigned long long)(unsigned)e.y << 32);
-#endif
   };
   load_spawn();
   {
+    // (the one-trip inner loops here and in updateShells are what is left of slot groups of two.  They stay in this change,
+    //  whose check is that the device code is the parent's instruction for instruction: with the loops collapsed the
+    //  compiler unrolls in another order and allocates registers differently.  profiles/closed_switches.md)
 #pragma unroll
-    for (int g = 0; g < SF_SPF / SF_SGSZ; g++) {
-      if (SF_ABL_PROJ < 2 && __ballot((L.smask & (((1u << SF_SGSZ) - 1u) << (SF_SGSZ * g))) != 0u) != 0ull) {
+    for (int g = 0; g < SF_SPF; g++) {
+      if (__ballot((L.smask & (1u << g)) != 0u) != 0ull) {
 #pragma unroll
-        for (int k = 0; k < SF_SGSZ; k++) {
-          const int s = SF_SGSZ * g + k;
+        for (int k = 0; k < 1; k++) {
+          const int s = g + k;
           const bool live = (L.smask >> s) & 1u;
           const d2_t sp = pld16(SF_GOFF(shell_pos, s), live);
           const d2_t sv = pld16(SF_GOFF(shell_vel, s), live);
@@ -1214,18 +1097,14 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
       }
     }
   }
-#if SF_LATE
   // ---- the late set, 2 + 2 SF_MROWS unconditional memory instructions behind everything the first phases wait for: the
   //      score and counts chunks, then the first SF_MROWS rows of the tile's missile pool -- lane l takes entry 64 r + l,
   //      (x, y) and the meta word, if the pool has that many (the count came with the early set): unconditional
   //      instructions, so the compiler can count them when it waits for the spawn entry issued ahead of them
   late = load_lane_late(tb, o);
   if (kPoolLoads) { SF_LOAD_POOL_ROWS(0, L.mpool) }
-#endif
 
-#if SF_ABL_TRIG == 0
   __syncthreads();  // the only workgroup barrier of the kernel
-#endif
   const double* trig = lds;
   SF_STAMP(3, false);
 
@@ -1241,7 +1120,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     if (step > 0) {
       // the pool rows the previous tick compacted in place: agent-scope loads (they bypass the wave's L1, where the rows
       // read a tick ago may still sit), in flight under the key / ship / fortress / shell arithmetic
-      if (SF_ABL_PROJ == 0 || SF_ABL_PROJ == 3) { SF_LOAD_POOL_ROWS(16, L.mpool) }
+      SF_LOAD_POOL_ROWS(16, L.mpool)
       will_respawn = !(L.fl & SF_FL_SHIP_ALIVE) && L.death_t >= sfc::explode_duration;
       load_spawn();
     }
@@ -1359,18 +1238,8 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   }
 
   // the two bearings the rest of the tick and the observation need, side by side (ILP)
-#if SF_ABL_ATAN == 2
-  double a_pos = (L.sy - sfc::fort_y) * 0.001 + (L.sx - sfc::fort_x) * 0.002;
-#else
   double a_pos = sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x, lds + kLdsAtab);
-#endif
-#if SF_ABL_ATAN
-  double a_vel = L.vy * 0.5 + L.vx;
-#elif SF_AXIS_VEL
-  double a_vel = sf_atan2<false>(L.vy, L.vx);
-#else
-  double a_vel = SF_FAST_ATAN ? sf_atan2_core(L.vy, L.vx, lds + kLdsAtab) : atan2(L.vy, L.vx);
-#endif
+  double a_vel = sf_atan2_core(L.vy, L.vx, lds + kLdsAtab);
 
   // ---- updateFortress (SRC/game.cpp:194-216)
   int new_s_slot = -1;
@@ -1426,7 +1295,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   d2_t pcs[SF_MROWS];
 #pragma unroll
   for (int r = 0; r < SF_MROWS; r++)
-    pcs[r] = (SPLIT || SF_ABL_PROJ == 1 || SF_ABL_PROJ == 2) ? d2_t{0, 0} : *reinterpret_cast<const d2_t*>(&trig[2 * SF_MM_ANGLE(pmeta[r])]);
+    pcs[r] = SPLIT ? d2_t{0, 0} : *reinterpret_cast<const d2_t*>(&trig[2 * SF_MM_ANGLE(pmeta[r])]);
 
   // the tick's first two score() calls (fireMissile's penalty, then a hexagon death), in their order, now that the
   // score chunk is needed anyway (shell kills and missile events follow)
@@ -1458,14 +1327,14 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     pst16_at(SF_GOFF(shell_vel, 0), new_s_slot >= 0, (unsigned)new_s_slot * 1024u, d2_t{new_s_vx, new_s_vy});
   {
 #pragma unroll
-    for (int g = 0; g < SF_SPF / SF_SGSZ; g++) {
-      const unsigned gmask = ((1u << SF_SGSZ) - 1u) << (SF_SGSZ * g);
-      if (SF_ABL_PROJ >= 2 || __ballot((L.smask & gmask) != 0u) == 0ull) continue;
+    for (int g = 0; g < SF_SPF; g++) {
+      const unsigned gmask = 1u << g;
+      if (__ballot((L.smask & gmask) != 0u) == 0ull) continue;
       unsigned col = 0, out = 0;
-      double nx[SF_SGSZ], ny[SF_SGSZ];
+      double nx[1], ny[1];
 #pragma unroll
-      for (int k = 0; k < SF_SGSZ; k++) {
-        const int s = SF_SGSZ * g + k;
+      for (int k = 0; k < 1; k++) {
+        const int s = g + k;
         const bool isnew = (s == new_s_slot);
         const double vx = isnew ? new_s_vx : shvx[s], vy = isnew ? new_s_vy : shvy[s];
         nx[k] = (isnew ? kv_fx : shx[s]) + vx;
@@ -1499,15 +1368,15 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
       }
       L.smask &= ~dead;
 #pragma unroll
-      for (int k = 0; k < SF_SGSZ; k++) {
-        const int s = SF_SGSZ * g + k;
+      for (int k = 0; k < 1; k++) {
+        const int s = g + k;
         pst16(SF_GOFF(shell_pos, s), (L.smask >> s) & 1u, d2_t{nx[k], ny[k]});
         if (draw_now)
           if (((L.smask >> s) & 1u) && sfd::hud_rows_near((float)ny[k], sfd::kShellExt))  // (all but never)
             dr_proj |= sfd::hud_flags_near((float)nx[k], (float)ny[k], sfd::kShellExt);
       }
     }
-    if (SF_ABL_PROJ < 2 && __ballot((L.smask >> SF_SPF) != 0u) != 0ull) {  // rare: more than SF_SPF shells in some lane
+    if (__ballot((L.smask >> SF_SPF) != 0u) != 0ull) {  // rare: more than SF_SPF shells in some lane
 #pragma unroll 1
       for (int s = SF_SPF; s < SF_NSLOT; s++) {
         const bool live = (L.smask >> s) & 1u;
@@ -1591,10 +1460,10 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
         typedef float f4_t __attribute__((ext_vector_type(4)));
         const unsigned doff = (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_MISSILE0 + SF_MM_SLOT(meta)) * (unsigned)SF_DR_PIECE_STRIDE +
                               SF_MM_OWNER(meta) * (unsigned)SF_DR_LANE_STRIDE;
-        sf_buf_st128<SF_DR_AUX>(__builtin_bit_cast(u4_t, (d2_t{nx, ny})), rs_draw, keep ? doff : SF_OOB, 0);
+        sf_buf_st128<0>(__builtin_bit_cast(u4_t, (d2_t{nx, ny})), rs_draw, keep ? doff : SF_OOB, 0);
         __builtin_amdgcn_raw_buffer_store_b16((short)SF_MM_ANGLE(meta), rs_draw,
                                               keep ? SF_DR_ANGLES_OFF + 2u * SF_MM_SLOT(meta) + SF_MM_OWNER(meta) * (unsigned)SF_DR_LANE_STRIDE : SF_OOB,
-                                              0, SF_DR_AUX);
+                                              0, 0);
         const bool rows = keep & sfd::hud_rows_near((float)ny, sfd::kMissileExt);
         if (__ballot(rows) != 0ull) {  // (all but never) -> bits 24..27 of the owner's hit word
           if (rows)
@@ -1609,7 +1478,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
       if (spins >= kSpinLimit && lane == 0u) atomicAdd(&a.acc[SF_ACC_HANDOVER], 1ull);
       asm volatile("" ::: "memory");
       wp = dw & 0x7FFFFFFFu;
-    } else if (SF_ABL_PROJ == 0 || SF_ABL_PROJ == 3) {
+    } else {
 #pragma unroll
       for (int r = 0; r < SF_MROWS; r++)
         if (m_live > 64u * r) m_row(prow[r].x, prow[r].y, pmeta[r], pcs[r], 64u * r + lane < m_live);
@@ -1796,9 +1665,9 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     const __amdgpu_buffer_rsrc_t rs_dr = __builtin_amdgcn_make_buffer_rsrc(
         a.draw + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * (size_t)SF_DR_TILE_BYTES, 0, SF_DR_TILE_BYTES, 0x00020000);
     const unsigned d0 = real ? lane * (unsigned)SF_DR_LANE_STRIDE : SF_OOB;
-    sf_buf_st128<SF_DR_AUX>(u4_t{h.w[0], h.w[1], h.w[2], h.w[3]}, rs_dr, d0, 0);
-    sf_buf_st128<SF_DR_AUX>(u4_t{h.w[4], h.w[5], h.w[6], h.w[7]}, rs_dr, d0, SF_DR_PIECE_STRIDE);
-    sf_buf_st128<SF_DR_AUX>(__builtin_bit_cast(u4_t, (d2_t{L.sx, L.sy})), rs_dr, d0, (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_SHIP) * SF_DR_PIECE_STRIDE);
+    sf_buf_st128<0>(u4_t{h.w[0], h.w[1], h.w[2], h.w[3]}, rs_dr, d0, 0);
+    sf_buf_st128<0>(u4_t{h.w[4], h.w[5], h.w[6], h.w[7]}, rs_dr, d0, SF_DR_PIECE_STRIDE);
+    sf_buf_st128<0>(__builtin_bit_cast(u4_t, (d2_t{L.sx, L.sy})), rs_dr, d0, (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_SHIP) * SF_DR_PIECE_STRIDE);
   }
   if (!FUSED) store_lane_buf(rs, o, L);
   SF_STAMP(14, false);
@@ -1827,14 +1696,11 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     }
   }
   SF_STAMP(7, false);
-  if constexpr (SF_ABL_OBS == 1) {  // timing-only: no observation at all
-  } else if constexpr (OBSK == 1) {  // the host guarantees: features, float32, n_envs % 64 == 0, aligned output (sf_launch_step)
+  if constexpr (OBSK == 1) {  // the host guarantees: features, float32, n_envs % 64 == 0, aligned output (sf_launch_step)
     constexpr int DIM = AUTOTURN ? 17 : 19;
     float* stage = reinterpret_cast<float*>(lds + kLdsStage);
-    if (SF_ABL_OBS != 3) {  // SF_ABL_OBS 3 (timing-only): the stores alone, of whatever the staging rows hold
-      const Extras e = compute_extras(a, L, a_pos, a_vel);
-      write_features_f32<DIM>(stage + tid * DIM, L, e, a.real_shell_count);
-    }
+    const Extras e = compute_extras(a, L, a_pos, a_vel);
+    write_features_f32<DIM>(stage + tid * DIM, L, e, a.real_shell_count);
     if ((i & ~63u) < (unsigned)n_envs_p)  // the padding waves behind the batch write nothing
       flush_features_f32<DIM>(stage + (tid & ~63u) * DIM, (float*)obs + (so + (i & ~63u)) * DIM, lane);
   } else if (obs != nullptr && a.obs_type != 3) {  // uniform across the grid
@@ -2462,12 +2328,12 @@ __global__ __launch_bounds__(64) void sf_lanes_load_kernel(SfKernelArgs a, const
       load_lane_early(stage, o, L);
       unpack_lane_late(load_lane_late(stage, o), L);
       // the bearings as the tick that made this state computed them: a new game's (time 0: sf_reset, an auto-reset) with the
-      // reset's atan2, any other with the step's table form (SF_FAST_ATAN); SF_FLAG_REF_RESET_OBS zeroes a new game's extras
+      // reset's atan2, any other with the step's table form; SF_FLAG_REF_RESET_OBS zeroes a new game's extras
       const bool fresh = L.time == 0;
       const double* atab = a.consts + SF_CONST_ATAB;
       const double a_pos = fresh ? sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x)
                                  : sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x, atab);
-      const double a_vel = fresh ? sf_atan2<false>(L.vy, L.vx) : (SF_FAST_ATAN ? sf_atan2_core(L.vy, L.vx, atab) : atan2(L.vy, L.vx));
+      const double a_vel = fresh ? sf_atan2<false>(L.vy, L.vx) : sf_atan2_core(L.vy, L.vx, atab);
       Extras x = compute_extras(a, L, a_pos, a_vel);
       if (fresh && a.ref_reset_obs) x = Extras{0.0, 0.0, 0.0};
       if (restored) {

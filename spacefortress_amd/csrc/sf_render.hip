@@ -33,27 +33,19 @@
 #include "sf_raster.h"
 #include "sf_tor_dev.h"
 
-// diagnostic builds only (tools/variant.py NAME -DSF_RENDER_SKIP=bits): bit 0 ship + fortress strokes, 1 missiles + shells,
-// 2 score, 3 bar, 4 the resampling, 5 the coverage of the dense rounds, 6 their compositing, 8 the dead ship's explosion,
-// 9 the fortress's explosion, 10 = explosion-cache misses take the hit path, 12 = no surface loads -- each bit removes that
-// part (wrong pixels) so that its cost can be read off
-#ifndef SF_RENDER_SKIP
-#define SF_RENDER_SKIP 0
-#endif
+// ---- the build's switches: two numeric tunables and one instrument (SF_RENDER_STOP) ----
 // diagnostic builds only: the frame kernel returns behind phase N (1 the prologue up to the barrier, 2 the cached explosion,
 // 3 the fresh explosions, 41 .. 44 inside draw_strokes, 4 the strokes of ship / fortress / missiles, 5 the shells) --
 // instruction counts of the phases by difference (tools/pmc_render_stops.sh)
-#ifndef SF_RESAMPLE_QUADS
-#define SF_RESAMPLE_QUADS 1
-#endif
-#ifndef SF_MERGE_SHELLS
-#define SF_MERGE_SHELLS 1
-#endif
 #ifndef SF_RENDER_STOP
 #define SF_RENDER_STOP 0
 #endif
 #ifndef SF_PREPASS_MAX_ENVS
 #define SF_PREPASS_MAX_ENVS 6144 /* batches up to here get the explosion pre-pass (sf_explosion_kernel): measured break-even near 8 192 */
+#endif
+#ifndef SF_RENDER_WPE
+#define SF_RENDER_WPE 3 /* waves per SIMD the register budget is held to (168 VGPRs, some thirty spilled: measured 184 against 202 us
+                            at two waves); LDS -- 14 KB per frame -- allows 11 workgroups per CU */
 #endif
 
 namespace {
@@ -190,11 +182,7 @@ struct Frame {
   // (OpenCV's resizeArea_ arithmetic: per source row buf = sum alpha * S, then sum += beta * buf in
   // table order, saturate_cast<uchar>).
   __device__ __forceinline__ void resample(const Box& b) const {
-    if (!SF_RESAMPLE_QUADS) {
-      resample_into(b, obuf, SF_OUT, 0, 0);
-      return;
-    }
-    if (!RESIZE || (SF_RENDER_SKIP & 16) || b.empty()) return;
+    if (!RESIZE || b.empty()) return;
     fill_ltab();
     // in groups of four pixels of a row (resample_quad): the box's columns widened to multiples of four
     const Box o = out_box(b);
@@ -243,7 +231,7 @@ struct Frame {
     const float sum = (b0 * h0 + b1 * h1) + b2 * h2;  // a two-row entry has b2 = 0: adds +0
     int v = (int)rintf(sum);                            // saturate_cast<uchar>: round half to even, clamp
     v = v < 0 ? 0 : (v > 255 ? 255 : v);
-    if (!(SF_RENDER_SKIP & 16384) || v == 77) dst[(unsigned)((dy - y_off) * stride + (dx - x_off))] = (uint8_t)v;  // (16384: timing only)
+    dst[(unsigned)((dy - y_off) * stride + (dx - x_off))] = (uint8_t)v;
   }
   __device__ __forceinline__ void resample_px(int dx, int dy, uint8_t* dst, int stride, int x_off, int y_off) const {
     resample_finish(taps_fetch(dx, dy), dx, dy, dst, stride, x_off, y_off);
@@ -277,32 +265,12 @@ struct Frame {
     const float b0 = __uint_as_float(tr.y), b1 = __uint_as_float(tr.z), b2 = __uint_as_float(tr.w);
     const uint8_t* r0 = fb + first + (int)tr.x * SF_IMG_W + (int)c0.x;
     unsigned long long w0, w1, w2;
-#ifndef SF_RQ_ALIGNED
-#define SF_RQ_ALIGNED 0 /* A/B: a row's eight bytes as three ALIGNED words + two v_alignbyte instead of one 8-byte read at any byte */
-#endif
-#if SF_RQ_ALIGNED
-    {
-      static_assert(SF_IMG_W % 4 == 2, "the rows' alignments below");
-      const unsigned A = (unsigned)(first + (int)tr.x * SF_IMG_W + (int)c0.x), al = A & 3u, al1 = (A + 2u) & 3u;  // (fb is 16-byte aligned)
-      const uint32_t* q0 = reinterpret_cast<const uint32_t*>(fb + (A & ~3u));
-      const uint32_t* q1 = reinterpret_cast<const uint32_t*>(fb + ((A + SF_IMG_W) & ~3u));
-      const uint32_t* q2 = reinterpret_cast<const uint32_t*>(fb + ((A + 2 * SF_IMG_W) & ~3u));
-      const unsigned a0 = q0[0], a1 = q0[1], a2 = q0[2], b0_ = q1[0], b1_ = q1[1], b2_ = q1[2], c0_ = q2[0], c1_ = q2[1], c2_ = q2[2];
-      w0 = (unsigned long long)__builtin_amdgcn_alignbyte(a1, a0, al) | ((unsigned long long)__builtin_amdgcn_alignbyte(a2, a1, al) << 32);
-      w1 = (unsigned long long)__builtin_amdgcn_alignbyte(b1_, b0_, al1) | ((unsigned long long)__builtin_amdgcn_alignbyte(b2_, b1_, al1) << 32);
-      w2 = (unsigned long long)__builtin_amdgcn_alignbyte(c1_, c0_, al) | ((unsigned long long)__builtin_amdgcn_alignbyte(c2_, c1_, al) << 32);
-    }
-#else
     __builtin_memcpy(&w0, r0, 8);
     __builtin_memcpy(&w1, r0 + SF_IMG_W, 8);
     __builtin_memcpy(&w2, r0 + 2 * SF_IMG_W, 8);
-#endif
-#ifndef SF_RQ_PERM
-#define SF_RQ_PERM 1 /* A/B: the pixel's two source bytes by v_perm_b32 (one selector for the three rows) instead of three 64-bit
-                        shifts, the rounded, saturated byte dropped into the word by v_cvt_pk_u8_f32 (round to nearest even,
-                        clamp to 0 .. 255: saturate_cast<uchar>(rint)) instead of rint + clamp + shift + or */
-#endif
-#if SF_RQ_PERM
+    // the pixel's two source bytes by v_perm_b32 (one selector for the three rows) instead of three 64-bit shifts, the
+    // rounded, saturated byte dropped into the word by v_cvt_pk_u8_f32 (round to nearest even, clamp to 0 .. 255:
+    // saturate_cast<uchar>(rint)) instead of rint + clamp + shift + or
     unsigned word = 0u;
     auto one = [&](const uint4& c, unsigned k) {
       // bytes off, off + 1 of the row's eight (off = 0 .. 4), the upper half zero (selector byte 0x0c)
@@ -321,25 +289,10 @@ struct Frame {
     one(c1, 1u);
     one(c2, 2u);
     one(c3, 3u);
-#else
-    auto one = [&](const uint4& c) -> unsigned {
-      const unsigned sh = 8u * (c.x - c0.x);  // 0 .. 32: the pixel's two source columns are bytes sh / 8 and sh / 8 + 1
-      const unsigned p0 = (unsigned)(w0 >> sh), p1 = (unsigned)(w1 >> sh), p2 = (unsigned)(w2 >> sh);
-      const float a0 = __uint_as_float(c.y), a1 = __uint_as_float(c.z);
-      const float h0 = (float)(p0 & 255u) * a0 + (float)((p0 >> 8) & 255u) * a1;
-      const float h1 = (float)(p1 & 255u) * a0 + (float)((p1 >> 8) & 255u) * a1;
-      const float h2 = (float)(p2 & 255u) * a0 + (float)((p2 >> 8) & 255u) * a1;
-      const float sum = (b0 * h0 + b1 * h1) + b2 * h2;
-      int v = (int)rintf(sum);
-      v = v < 0 ? 0 : (v > 255 ? 255 : v);
-      return (unsigned)v;
-    };
-    const unsigned word = one(c0) | (one(c1) << 8) | (one(c2) << 16) | (one(c3) << 24);
-#endif
     *reinterpret_cast<uint32_t*>(obuf + (unsigned)(dy * SF_OUT + dx0)) = word;
   }
   __device__ __forceinline__ void resample_into(const Box& b, uint8_t* dst, int stride, int x_off, int y_off) const {
-    if (!RESIZE || (SF_RENDER_SKIP & 16) || b.empty()) return;
+    if (!RESIZE || b.empty()) return;
     const Box o = out_box(b);
     const int ox0 = o.x0, oy0 = o.y0;
     const int ow = o.x1 - o.x0, n = ow * (o.y1 - o.y0);
@@ -378,10 +331,7 @@ struct Frame {
     // its life) draws nothing and is left out: no record, no sub-rows, and a frame with nothing else makes no call at all
     const unsigned long long drawn = __ballot(mineok);
     const int nq = kind == sftd::kKindShell ? 4 : 3;  // (per lane: the object's)
-#ifndef SF_CULL_OFFSCREEN
-#define SF_CULL_OFFSCREEN 1
-#endif
-    const bool obj_seen = !SF_CULL_OFFSCREEN || ((drawn >> obj0) & ((1ull << nq) - 1ull)) != 0ull;
+    const bool obj_seen = ((drawn >> obj0) & ((1ull << nq) - 1ull)) != 0ull;
     unsigned long long live = __ballot(valid && obj_seen);
     SF_DS_STAMP(0);
     while (live) {
@@ -398,7 +348,7 @@ struct Frame {
     // enumeration over the destination pixels of all the objects' boxes: prefix sum, starts in LDS, a lane per pixel finds its
     // object --, everything being drawn by now (a destination pixel that reads a changed source pixel lies in some object's box).
     SF_DS_STAMP(3);
-    if (RESIZE && !(SF_RENDER_SKIP & 16) && drawn) {
+    if (RESIZE && drawn) {
       fill_ltab();  // (behind the objects' records and map of this pass: nothing below writes there)
       const bool me = (drawn >> lane) & 1ull;
       int ux0 = me ? myb.x0 : (1 << 20), uy0 = me ? myb.y0 : (1 << 20), ux1 = me ? myb.x1 : -1, uy1 = me ? myb.y1 : -1;
@@ -422,9 +372,9 @@ struct Frame {
         }
       }
       const Box o = out_box(Box{ux0, uy0, ux1, uy1});
-      // (SF_RESAMPLE_QUADS: the unit of the enumeration is four pixels of a row, at multiples of four: resample_quad)
-      const int ogx0 = SF_RESAMPLE_QUADS ? o.x0 >> 2 : o.x0;
-      const int ow = SF_RESAMPLE_QUADS ? ((o.x1 + 3) >> 2) - ogx0 : o.x1 - o.x0;
+      // (the unit of the enumeration is four pixels of a row, at multiples of four: resample_quad)
+      const int ogx0 = o.x0 >> 2;
+      const int ow = ((o.x1 + 3) >> 2) - ogx0;
       const int on = (head && ux1 > ux0 && uy1 > uy0) ? ow * (o.y1 - o.y0) : 0;
       unsigned long long todo = __ballot(on > 0);
       while (todo) {
@@ -460,8 +410,7 @@ struct Frame {
           if (i < total) {
             const int4 rec = *reinterpret_cast<const int4*>(orec + 4 * k);
             const DivMod dm = fast_divmod(i - rec.z, rec.y, __int_as_float(rec.w));
-            if (SF_RESAMPLE_QUADS) resample_quad(4 * ((rec.x & 255) + dm.r), (rec.x >> 8) + dm.q);
-            else resample_px((rec.x & 255) + dm.r, (rec.x >> 8) + dm.q, obuf, SF_OUT, 0, 0);
+            resample_quad(4 * ((rec.x & 255) + dm.r), (rec.x >> 8) + dm.q);
           }
         }
         __builtin_amdgcn_wave_barrier();
@@ -611,7 +560,10 @@ __device__ __forceinline__ XcState ship_explosion(const Frame<RESIZE>& F, const 
     const double kx = *reinterpret_cast<const double*>(xc + kXcKey), ky = *reinterpret_cast<const double*>(xc + kXcKey + 8);
     const unsigned fl = *reinterpret_cast<const unsigned*>(xc + kXcFlags);
     const int2 keys = *reinterpret_cast<const int2*>(xc + kXcHudKeys);
-    hit = (kx == x && ky == y && (fl & need) == need) || (SF_RENDER_SKIP & 1024);  // (bit 10: a miss costs what a hit does)
+    // (`|| false` is what is left of a timing switch.  It stays in this change, whose check is that the device code is the
+    //  parent's instruction for instruction: without it the compiler builds the test as a value instead of as branches and
+    //  allocates registers differently in three kernels.  profiles/closed_switches.md)
+    hit = (kx == x && ky == y && (fl & need) == need) || false;
     st = XcState{fl, keys.x, keys.y};
   }
   // (put_row_word: rows of sixteen bytes or more, see kXcRowW -- a ship dies inside the big hexagon, 5 pixels or more from the
@@ -700,7 +652,7 @@ __device__ __forceinline__ bool xc_apply(const Frame<RESIZE>& F, const XcFetch& 
   const Box b = explosion_box(cx, cy), o = out_box(b);
   const int lane = F.lane;
   const unsigned need = RESIZE ? 3u : 1u;
-  const bool hit = (f.kx == x && f.ky == y && (f.fl & need) == need) || (SF_RENDER_SKIP & 1024);
+  const bool hit = (f.kx == x && f.ky == y && (f.fl & need) == need) || false;  // (`|| false`: as in ship_explosion)
   const bool fits = b.x1 - b.x0 <= kXcRow && b.y1 - b.y0 <= kXcFbRows && o.x1 - o.x0 <= kXcRow && o.y1 - o.y0 <= kXcOutRows &&
                     b.x1 - b.x0 >= 16 && o.x1 - o.x0 >= 16;
   if (!(hit && fits)) return false;
@@ -738,13 +690,6 @@ __device__ __forceinline__ Pieces load_pieces(const uint4* src, int n, int lane)
   return Pieces{src[min(lane, last)],       src[min(lane + 64, last)],  src[min(lane + 128, last)], src[min(lane + 192, last)],
                 src[min(lane + 256, last)], src[min(lane + 320, last)], src[min(lane + 384, last)]};
 }
-#ifndef SF_FRAME_NT
-#define SF_FRAME_NT 1 /* the 84x84 background's stores leave non-temporal when the frame is a slot of a frame stack (out_stride >
-                         a frame): the 4-frame ring of 16 384 envs is 462 MB that cycle through the 256 MB Infinity Cache and
-                         push out what the step and the frame kernel read every step -- 52.3 -> 51.2 us per step into the
-                         ring.  A flat output (115 MB, rewritten in place every step) stays resident and wants plain stores:
-                         non-temporal there costs +1.1 us.  0: always plain; 2: always non-temporal (A/B) */
-#endif
 template <bool NT>
 __device__ __forceinline__ void store_piece(uint4* p, const uint4& v) {
   if (NT) {
@@ -1051,10 +996,6 @@ static_assert(((SF_BAR_BOX_Y1 - SF_BAR_BOX_Y0) * SF_HUD_BAR_ROW + 15) / 16 * 16 
               "bar picture layout");
 
 template <bool RESIZE>
-#ifndef SF_RENDER_WPE
-#define SF_RENDER_WPE 3 /* waves per SIMD the register budget is held to (168 VGPRs, some thirty spilled: measured 184 against 202 us
-                            at two waves); LDS -- 14 KB per frame -- allows 11 workgroups per CU */
-#endif
 __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t fbw[kFbPadWords];
   const uint32_t* const tabw = a.tabs;  // 2.7 KB read by every wave: L1/L2 resident; LDS is better spent on waves
@@ -1069,19 +1010,6 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
     const int ti = lane < Frame<RESIZE>::kLtabCols ? lane : min(SF_OUT + lane - Frame<RESIZE>::kLtabCols, SF_OUT + 20);
     lt_e = reinterpret_cast<const uint4*>(a.tabs)[ti];
   }
-#ifndef SF_RENDER_STAGGER
-#define SF_RENDER_STAGGER 0 /* A/B: the first generation's workgroups (16 per CU, all launched at once) start in four phases
-                               SF_RENDER_STAGGER x 64 cycles apart, by SF_RENDER_STAGGER_SHIFT bits of the workgroup's index */
-#endif
-#ifndef SF_RENDER_STAGGER_SHIFT
-#define SF_RENDER_STAGGER_SHIFT 10
-#endif
-#if SF_RENDER_STAGGER
-  if (blockIdx.x < 4096u) {
-    const unsigned ph = (blockIdx.x >> SF_RENDER_STAGGER_SHIFT) & 3u;  // uniform
-    for (unsigned k = 0; k < ph; k++) __builtin_amdgcn_s_sleep(SF_RENDER_STAGGER);
-  }
-#endif
   // ---- which env (pick_env).  Nearly every workgroup behind the front draws env = its index - n_front, and learns that
   // from one word of the hint: the record's loads go out for that env at once, next to the word's load, instead of behind it.
   int env = blockIdx.x;
@@ -1134,9 +1062,9 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   }
   const float ship_x = __uint_as_float(hd[SF_DRW_SHIP_X]), ship_y = __uint_as_float(hd[SF_DRW_SHIP_Y]);
   const int pnts = (int)hd[SF_DRW_POINTS];
-  const unsigned objmask = (SF_RENDER_SKIP & 2) ? (hd[SF_DRW_OBJMASK] & 3u) : hd[SF_DRW_OBJMASK];
+  const unsigned objmask = hd[SF_DRW_OBJMASK];
   const unsigned mmask = objmask >> SF_DR_OBJ_MISSILE0;
-  const unsigned shw = hd[SF_DRW_SHELLS], smask = (SF_RENDER_SKIP & 2) ? 0u : (shw & SF_MASK_LOW);
+  const unsigned shw = hd[SF_DRW_SHELLS], smask = shw & SF_MASK_LOW;
   const unsigned fl = hd[SF_DRW_FLAGS];
   const int bgi = (int)SF_DRF_BG(fl), bstate = (int)SF_DRF_BAR(fl);
   const bool dead_ship = !(fl & SF_DRF_SHIP_ALIVE);
@@ -1150,7 +1078,7 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   // seventeen live shells -- have a late round of their own) -- unless the top lanes of the missiles' range are free for
   // them (the record's SF_DRF_MERGE_SHELLS: nearly always): then their strokes sit there, behind the missiles' as in the draw
   // order, and go through draw_strokes with everything else instead of a call, a chunk, a resample pass of their own
-  const bool merge_shells = SF_MERGE_SHELLS && (fl & SF_DRF_MERGE_SHELLS);
+  const bool merge_shells = fl & SF_DRF_MERGE_SHELLS;
   const int shl = merge_shells ? lane - (int)(shw >> 24) : lane;  // 4 * slot + stroke, negative = not a shell's lane
   const unsigned char* const tile = a.state + (long)(env >> 6) * sfl::kTileBytes;  // (the shells' positions live in the state)
   const int o16 = (env & 63) * 16;
@@ -1210,11 +1138,8 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   // the score's and the bar's pictures, when they will not be the baked-in 0000000 / empty ones: used last, asked for now
   const Box tbox{SF_TXT_BOX_X0, SF_TXT_BOX_Y0, SF_TXT_BOX_X1, SF_TXT_BOX_Y1};
   const Box bbox{SF_BAR_BOX_X0, SF_BAR_BOX_Y0, SF_BAR_BOX_X1, SF_BAR_BOX_Y1};
-#ifndef SF_HUD_PREFETCH
-#define SF_HUD_PREFETCH 1
-#endif
-  const bool score_pre = SF_HUD_PREFETCH && a.hud && pnts != 0 && pnts >= -SF_HUD_SCORE_HALF && pnts < SF_HUD_SCORE_HALF && !(SF_RENDER_SKIP & 4);
-  const bool bar_pre = SF_HUD_PREFETCH && a.hud && bstate != 0 && !(SF_RENDER_SKIP & 8);
+  const bool score_pre = a.hud && pnts != 0 && pnts >= -SF_HUD_SCORE_HALF && pnts < SF_HUD_SCORE_HALF;
+  const bool bar_pre = a.hud && bstate != 0;
   // (in front of the background's pieces, for what is restored right behind the barrier or at the very end: the dead ship's
   //  cached explosion -- key and pixels together, the pixels used if the key matches --, the score's and the bar's pictures)
   XcFetch xf = {};
@@ -1224,11 +1149,11 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   if (bar_pre) hbar = hud_fetch<RESIZE>(hud_bar_picture(a.hud, bstate), SF_HUD_BAR_ROW, bbox, lane);
   // the 84x84 background's seven pieces
   Pieces frame0 = {};
-  if (RESIZE && !(SF_RENDER_SKIP & 8192)) frame0 = load_pieces(reinterpret_cast<const uint4*>(a.bg84 + bgi * (kOutBytes / 4)), kOutBytes / 16, lane);  // (bit 13: timing-only, no background copy)
+  if (RESIZE) frame0 = load_pieces(reinterpret_cast<const uint4*>(a.bg84 + bgi * (kOutBytes / 4)), kOutBytes / 16, lane);
   // ... and LAST of the round trip, the surface's ten direct-to-LDS loads: a wave's loads come back in issue order and the
   // compiler does not know of these ten, so every wait it counts out for something issued before them stays a wait for
   // that alone.
-  if (!(SF_RENDER_SKIP & 4096)) start_surface(bgi);  // (bit 12: timing-only, no surface)
+  start_surface(bgi);
 
   // ---- the shells' strokes, built here with the surface's loads in flight
   sft::Quad sq0 = {};
@@ -1253,8 +1178,12 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   }
   // the 84x84 background's seven stores, behind everything: stores count like loads, in the same order -- in front of the
   // surface's loads, the wait for the surface would be a wait for their acknowledgement from HBM as well
-  if (RESIZE && !(SF_RENDER_SKIP & 8192)) {
-    if (SF_FRAME_NT == 2 || (SF_FRAME_NT == 1 && a.out_stride > (size_t)kOutBytes))  // uniform: a slot of a frame stack (SF_FRAME_NT)
+  if (RESIZE) {
+    // the 84x84 background's stores leave non-temporal when the frame is a slot of a frame stack (out_stride > a frame):
+    // the 4-frame ring of 16 384 envs is 462 MB that cycle through the 256 MB Infinity Cache and push out what the step
+    // and the frame kernel read every step -- 52.3 -> 51.2 us per step into the ring.  A flat output (115 MB, rewritten
+    // in place every step) stays resident and wants plain stores: non-temporal there costs +1.1 us.
+    if (a.out_stride > (size_t)kOutBytes)  // uniform: a slot of a frame stack
       store_pieces<true>(frame0, reinterpret_cast<uint4*>(frame_out), kOutBytes / 16, lane);
     else
       store_pieces<false>(frame0, reinterpret_cast<uint4*>(frame_out), kOutBytes / 16, lane);
@@ -1282,7 +1211,7 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   // drawn in place, the missiles' (SRC/draw.cpp:233-247) -- the lane's corners under the object's transform, translate(pos)
   // rotate(angle) (drawWireFrame, SRC/draw.cpp:112-129), in device pixels
   const bool fort_lane = lane >= 3 && lane < kFirstMissileLane;
-  const bool svalid = ((objmask >> obj) & 1u) && !fort_lane && !((SF_RENDER_SKIP & 1) && lane < kFirstMissileLane);
+  const bool svalid = ((objmask >> obj) & 1u) && !fort_lane;
   const int sobj = lane < 3 ? 0 : (lane < kFirstMissileLane ? 3 : kFirstMissileLane + 3 * mslot);
   sft::Quad mq = {};
   if (svalid) {
@@ -1305,7 +1234,7 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   // everything but these stores is done -- the surface is in LDS -- without waiting for the stores to be acknowledged.  The
   // byte stores that follow land on top of them anyway: one wave's stores to one address are performed in program order.
   static_assert(kFrameRounds == 7 && 6 * 64 < kOutBytes / 16, "all seven stores have lanes to do");
-  if (RESIZE && !stack_traffic && !(SF_RENDER_SKIP & 8192)) {
+  if (RESIZE && !stack_traffic) {
     asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1327,17 +1256,14 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
 
   // (sf_tor_dev.h's accumulators start out zero and every call leaves them so; what lies below them -- records, headers,
   //  objects, task list, map -- is written by every call before it is read: twenty rounds of stores a frame that bought nothing)
-#ifndef SF_TOR_ZERO_ALL
-#define SF_TOR_ZERO_ALL 0
-#endif
-  for (int i = (SF_TOR_ZERO_ALL ? 0 : sftd::kAccAtF) + lane; i < Frame<RESIZE>::kTorWords; i += 64) torw[i] = 0u;
+  for (int i = sftd::kAccAtF + lane; i < Frame<RESIZE>::kTorWords; i += 64) torw[i] = 0u;
   __builtin_amdgcn_wave_barrier();
   // ---- what is restored from round trip 2's registers: the dead ship's explosion if its cache entry is this one
   // (the entry is keyed by where the ship died: the float64 position the picture is a function of)
   const double ship_xd = shipd.x, ship_yd = shipd.y;
   XcState xst{0u, 0, 0};
   bool explosion_done = false;
-  const bool explosion = dead_ship && !(SF_RENDER_SKIP & (1 | 256));
+  const bool explosion = dead_ship;
   if (explosion && xc_mine) explosion_done = xc_apply(F, xf, ship_xd, ship_yd, &xst);
   if (SF_RENDER_STOP == 2) return;
   // ---- ship (SRC/draw.cpp:233-237): a dead ship's explosion that was not in the cache is the first thing drawn
@@ -1346,9 +1272,9 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   // the layout of the per-env explosion cache (a trained agent destroys it every few seconds -- 30 frames each time).
   // Restored when what the ship drew stays clear of it (wider by the reach: what its 84x84 pixels read) -- the two touch no
   // pixel in common then, so it may go in before the ship --; else drawn in place between the ship and the missiles.
-  if ((fl & SF_DRF_FORT_EX_PATCH) && !(SF_RENDER_SKIP & (1 | 512)))
+  if (fl & SF_DRF_FORT_EX_PATCH)
     ship_explosion(F, a.arcs, const_cast<unsigned char*>(a.fpatch) + 36 * SF_FP_BYTES, sfc::fort_x, sfc::fort_y, false);
-  const bool fort_explodes_in_place = (fl & SF_DRF_FORT_EX_PLACE) && !(SF_RENDER_SKIP & (1 | 512));
+  const bool fort_explodes_in_place = fl & SF_DRF_FORT_EX_PLACE;
   if (SF_RENDER_STOP == 3) return;
   // ---- the live ship, the fortress in place, the missiles (:233-247): all their strokes at once
   const bool fort_lines_in_place = (objmask >> SF_DR_OBJ_FORT) & 1u;
@@ -1361,7 +1287,7 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
     else fort_in_place(F, a.falpha, min(max((int)(int16_t)(hd[SF_DRW_ANGLES] >> 16) / 10, 0), 35));
     F.draw_strokes(mq, dvalid && lane >= kFirstMissileLane, dobj, dkind);
   }
-  if ((fl & SF_DRF_MISSILE19) && !(SF_RENDER_SKIP & 2)) {  // (the twentieth missile: its strokes have no lanes of their own)
+  if (fl & SF_DRF_MISSILE19) {  // (the twentieth missile: its strokes have no lanes of their own)
     const d2_t t19 = *reinterpret_cast<const d2_t*>(rec + (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_MISSILE0 + 19) * SF_DR_PIECE_STRIDE);
     const int h19 = *reinterpret_cast<const int16_t*>(rec + SF_DR_ANGLES_OFF + 2 * 19);
     const sft::Quad q19 = line_quad(missile_seg(lane < 3 ? lane : 0), t19.x, t19.y, a.trig, h19);
@@ -1391,7 +1317,7 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   // belongs to (where the ship died, the points / the bar's state): drawn in place once, kept in the env's explosion
   // cache entry, restored for the other frames.
   // (one call site each for drawing and for the picture copy: what to do is decided first)
-  if (!(fl & SF_DRF_BAKED_TEXT) && !(SF_RENDER_SKIP & 4)) {
+  if (!(fl & SF_DRF_BAKED_TEXT)) {
     constexpr unsigned kBits = RESIZE ? 12u : 4u;
     const bool near_text = fl & SF_DRF_NEAR_TEXT, ex_text = fl & SF_DRF_EX_TEXT, other_text = fl & SF_DRF_OTHER_TEXT;
     unsigned char* pic = nullptr;
@@ -1416,7 +1342,7 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
       }
     }
   }
-  if (!(fl & SF_DRF_BAKED_BAR) && !(SF_RENDER_SKIP & 8)) {
+  if (!(fl & SF_DRF_BAKED_BAR)) {
     constexpr unsigned kBits = RESIZE ? 48u : 16u;
     const bool near_bar = fl & SF_DRF_NEAR_BAR, ex_bar = fl & SF_DRF_EX_BAR, other_bar = fl & SF_DRF_OTHER_BAR;
     const int state = bstate;

@@ -23,6 +23,11 @@
 
 #include "sf_tor.h"
 
+// the one switch of this file, an instrument (the per-phase times / instruction counts in NOTES.md)
+#ifndef SFTD_STOP
+#define SFTD_STOP 9 /* diagnostic builds: leave raster() behind phase N (0: at once, 1 records + boxes, 2 rows, 3 sub-rows) */
+#endif
+
 namespace sftd {
 
 constexpr int kMaxQuads = 16, kMaxObjs = 16;  // (the default geometry's kernel; the general one takes kMaxQuadsBig)
@@ -171,9 +176,6 @@ __device__ __forceinline__ unsigned band_sources(int okind, unsigned seams) {
 
 // MAXACT: how many quads of one object a pixel row taken whole may hold (4: lines; 8: a circle at a large scale -- more and the
 // row is sampled in sub-rows instead, which cairo does not do: the general kernel's circles stay below)
-#ifndef SFTD_STOP
-#define SFTD_STOP 9 /* diagnostic builds: leave raster() behind phase N (0: at once, 1 records + boxes, 2 rows, 3 sub-rows) */
-#endif
 template <int MAXACT = 4, bool kBand = false>
 __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool valid, int obj0, int kind, int grey, const Band& band = Band{}) {
   if (SFTD_STOP == 0) return;
@@ -520,11 +522,7 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
 //   * a row taken whole is handed to one lane per (row, quad) for its two trapezoid edges; rows in which two quads of an object
 //     overlap while taken whole (rare: the overlap of two lines is shorter than a pixel) go to one lane with the general code;
 //   * spans are added with straight-line code for the one- and two-pixel cases.
-#ifndef SFTD_FAST_QUADS
-#define SFTD_FAST_QUADS 16 /* quads per call of the fast arrangement (A/B: 32 -- fewer calls in crowded frames, 4.4 KB more LDS) */
-#endif
-constexpr int kMaxQuadsF = SFTD_FAST_QUADS;
-constexpr int kAccPixelsF = SFTD_FAST_QUADS > 16 ? 1024 : kAccPixels;  // (ten wireframes' boxes instead of five)
+constexpr int kMaxQuadsF = 16;  // quads per call of the fast arrangement
 constexpr int kRecWordsF = 48;
 // A quad's record:
 //    0 .. 15   the slots L1 L2 R1 R2: an edge as two doubles (A - 1/2, B): cell(s) = round(A' + B s)   (cell_fast)
@@ -543,7 +541,7 @@ constexpr int kTasksF = 64;     // (row, quad) pairs taken whole, per round
 constexpr int kMapWordsF = 64;  // the sub-rows' enumeration: a bit per start of a quad's run, 2 048 sub-rows per round
 static_assert(kMapWordsF <= kTasksF + 8, "the sub-rows' map lies over the rows' task list (one is dead when the other is written)");
 constexpr int kAccAtF = kMaxQuadsF * (kRecWordsF + 2 * kHdrWordsF) + kMaxObjs * kObjWordsF + kTasksF + 8;
-constexpr int kLdsWordsF = kAccAtF + kAccPixelsF / 2;
+constexpr int kLdsWordsF = kAccAtF + kAccPixels / 2;
 
 struct CtxF {
   uint32_t* lds;
@@ -564,11 +562,7 @@ struct CtxF {
 
 // inclusive prefix sum across the wave: six DPP adds (row_shr 1, 2, 4, 8; row_bcast 15 into rows 1 and 3, 31 into rows 2 and 3) --
 // no trips through LDS (__shfl_up is a ds_bpermute a step: six dependent LDS round trips for one scan)
-#ifndef SFTD_DPP_SCANS
-#define SFTD_DPP_SCANS 1
-#endif
 __device__ __forceinline__ int wave_incl_sum(int v) {
-#if SFTD_DPP_SCANS
 #define SFTD_SCAN_STEP(ctrl, rmask) v += __builtin_amdgcn_update_dpp(0, v, (ctrl), (rmask), 0xf, false)
   SFTD_SCAN_STEP(0x111, 0xf);
   SFTD_SCAN_STEP(0x112, 0xf);
@@ -578,15 +572,6 @@ __device__ __forceinline__ int wave_incl_sum(int v) {
   SFTD_SCAN_STEP(0x143, 0xc);
 #undef SFTD_SCAN_STEP
   return v;
-#else
-  const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int a = __shfl_up(v, d);
-    if (lane >= d) v += a;
-  }
-  return v;
-#endif
 }
 
 constexpr double kMagic52 = 6755399441055744.0;  // 1.5 * 2^52: adding it leaves round-to-nearest(x) in the low word
@@ -656,24 +641,15 @@ __device__ __forceinline__ void row_slots(const uint32_t* rc, int row, int* ls, 
 }
 
 // `mine`: this lane's quad (valid lanes); obj0: the first lane of its object (lanes of an object are consecutive)
-#ifndef SFTD_FAST_CALL
-#define SFTD_FAST_CALL 0 /* A/B: 1 = raster_fast as ONE function the frame kernel calls from its twelve places instead of twelve copies */
-#endif
 // what the pixels' pass needs of a call whose earlier passes ran apart from it (raster_fast<1>, then raster_fast_pixels: the frame
 // kernel's explosion pre-pass has eight waves rasterise a ring each into accumulators of their own and composite in draw order)
 struct RasterCarry {
   int nobj, tot_pix;
 };
 __device__ __forceinline__ void raster_fast_pixels(const CtxF& C, int nobj, int tot_pix);
-#if SFTD_FAST_CALL
-__device__ __attribute__((noinline)) void raster_fast(const CtxF C, const sft::Quad mine, bool valid, int obj0, int kind, int grey) {
-  constexpr int PHASE = 0;
-  RasterCarry* const carry = nullptr;
-#else
 template <int PHASE = 0>  // 0: the whole call; 1: everything but the pixels' pass (*carry says what is left)
 __device__ __forceinline__ void raster_fast(const CtxF& C, const sft::Quad& mine, bool valid, int obj0, int kind, int grey,
                                             RasterCarry* carry = nullptr) {
-#endif
   if (PHASE == 1) *carry = RasterCarry{0, 0};
   if (SFTD_STOP == 0) return;
   const int lane = C.lane, xmax = C.W * 256;
@@ -1062,15 +1038,12 @@ __device__ __forceinline__ void raster_fast(const CtxF& C, const sft::Quad& mine
   // a quarter to a half of its sub-rows.  Where a quad's whole rows are one block (always, for a stroke; anything else keeps one run
   // and the per-sub-row test below) its run is cut in two, [s_lo, the block) and [behind the block, s_hi): counts, scans, the
   // headers the sub-rows' lanes read -- first all the upper parts, then all the lower ones.
-#ifndef SFTD_SPLIT_RUNS
-#define SFTD_SPLIT_RUNS 1
-#endif
   int cnt = 0, s_lo = 0, cnt_b = 0, s_b = 0;
   if (valid) {
     s_lo = max(my_lo, 0);
     const int s_hi = min(my_hi, C.H * sft::kGridY);
     cnt = max(s_hi - s_lo, 0);
-    if (SFTD_SPLIT_RUNS && cnt > 0) {
+    if (cnt > 0) {
       const uint32_t* ob = C.obj(oi);
       const int oby0 = (int)((ob[0] >> 8) & 255u);
       const int r0 = ((s_lo * 34953) >> 19) - oby0, r1 = (((s_hi - 1) * 34953) >> 19) - oby0;  // the quad's rows within its object
