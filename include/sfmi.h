@@ -124,6 +124,27 @@ int sf_max_ticks(const sf_batch* b); /* ENV:165 -> 5294 */
  *      prev_vlner kept).  obs_dev: [n_envs, obs_dim] f32 (f64 with SF_FLAG_OBS_F64), may be NULL. ---- */
 int sf_reset(sf_batch* b, void* obs_dev, void* stream);
 
+/* ---- env.reset() in the envs the caller chooses (ENV:163-178), the others play on: the masked reset (`reset_idx`,
+ *      `reset(mask=...)` of other batched simulators; in the reference, env.reset() in one worker).
+ *      mask_dev: uint8 [n_envs] on the device; ANY non-zero byte means "this env calls env.reset() now".
+ *      A masked env: its state afterwards is what sf_reset gives that lane from the same prior state -- a brand-new Game,
+ *        prev_vlner kept, the next entry of the spawn stream taken at the lane's own cursor, the per-episode counters and
+ *        sums started over; its missiles leave the tile's pool.
+ *      An unmasked env: every byte of its state is as before -- missiles (position, heading, slot), shells, counters, cursor.
+ *        Where its missiles sit inside the tile's pool may change; nothing a row of sf_save_lanes or a later step can observe
+ *        does.  Every env plays the game it would play alone.
+ *      obs_dev (may be NULL): feature observations: the rows of the masked envs get the new game's observation exactly as
+ *        sf_reset writes it (SF_FLAG_REF_RESET_OBS, SF_FLAG_OBS_F64 included); no other row is written.  Image batches: the
+ *        draw records follow the new state at once; with obs_dev every env's frame is drawn from its state (the masked envs'
+ *        are the new game's, the others' what sf_render gives).  The explosion cache is keyed by the dead ship's position and
+ *        the render-order hint bits of the masked envs are cleared: a reset env is never served a stale picture.
+ *      Not changed: the finished-episode accumulators of sf_episode_stats (an abandoned game is not a finished episode), the
+ *        sticky overflow count of sf_check_state (only sf_reset clears it), the action sampler's tick (sf_seed_actions).
+ *      Plain stream work on `stream`: no allocation, no host read of the mask, no synchronise; capturable in a HIP graph.
+ *      This is what puts a finished lane of a SF_FLAG_NO_AUTO_RESET batch back to work without ending the other games.
+ *      SF_ERR_ARG (with a text): a NULL batch or mask_dev. ---- */
+int sf_reset_lanes(sf_batch* b, const uint8_t* mask_dev, void* obs_dev, void* stream);
+
 /* ---- VecEnv.step(actions): SSF_Env.step in every worker (ENV:208-253 -> press_key/release_key x4|x2
  *      + step_one_tick(34) + is_game_over, SRC/pymodule.cpp:199-240 -> Game::stepOneTick
  *      SRC/game.cpp:473-485), reward shaping (ENV:233-244), feature vector (ENV:95-157) and the
@@ -535,6 +556,7 @@ int sf_gather_errors(uint64_t* count_out, int clear, void* stream);
  *      The update is plain stream work on `stream` of the log's device: no allocation, no synchronise, capturable in a HIP
  *      graph (total and rows_seen advance on the device, so a replay goes on counting).
  *      sf_eplog_restart zeroes the running accumulators only (the envs start new games otherwise than by `done`);
+ *      (its masked form beside sf_reset_lanes, sf_eplog_restart_where, is declared in sfmi_masked.h);
  *      sf_eplog_clear the ring, the histogram, total and rows_seen as well.  sf_eplog_read synchronises `stream` and copies
  *      out total, rows_seen, the ring AS STORED (capacity records; slot s % capacity) and the histogram; any pointer may be
  *      NULL.  SF_ERR_ARG (with a text): n_envs outside [1, 2^26], capacity outside [1, 2^32], hist_bins outside [1, 65536],

@@ -92,6 +92,7 @@ SYMBOLS = {
     "sf_tick_ms": (C.c_int, [C.c_void_p]),
     "sf_max_ticks": (C.c_int, [C.c_void_p]),
     "sf_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sf_reset_lanes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sf_check_actions": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -171,6 +172,16 @@ SYMBOLS = {
     "sf_build_id": (C.c_char_p, []),
 }
 
+# every symbol include/sfmi_masked.h declares (the masked companions of sf_reset_lanes): bound like SYMBOLS
+MASKED_SYMBOLS = {
+    "sf_eplog_restart_where": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+# what the wrappers answer to `.reset_lanes`: their per-env memory would go stale behind a masked reset
+NO_RESET_LANES = ("%s has no reset_lanes(): its per-env memory (frame stacks, return accumulators, start flags, masks) has no "
+                  "rule for a masked reset yet.  Call SFVecEnv.reset_lanes on the bare env and rebuild the wrapper's state, or "
+                  "use reset()")
+
 _lib = None
 
 
@@ -183,7 +194,7 @@ def lib():
                 "libsfmi.so is missing (%s): build it with `python -m spacefortress_amd.build` "
                 "(there is no CPU fallback)" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(MASKED_SYMBOLS.items()):
             if not hasattr(L, name) and os.environ.get("SFMI_LIB_PATH"):
                 continue  # an older diagnostic build (A/B against an earlier round's library): entry points added since
             f = getattr(L, name)

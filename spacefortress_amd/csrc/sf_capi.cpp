@@ -821,6 +821,31 @@ extern "C" int sf_reset(sf_batch* b, void* obs_dev, void* stream) {
   return SF_OK;
 }
 
+extern "C" int sf_reset_lanes(sf_batch* b, const uint8_t* mask_dev, void* obs_dev, void* stream) {
+  if (!b) {
+    sf_set_error("sf_reset_lanes: null batch");
+    return SF_ERR_ARG;
+  }
+  if (!mask_dev) {
+    sf_set_error("sf_reset_lanes: null mask (uint8 [n_envs] on the device; sf_reset restarts every env)");
+    return SF_ERR_ARG;
+  }
+  DeviceGuard guard(b->device);
+  const bool image = is_image(b);
+  SF_FLUSH_VIEW(b, stream);  // (the kept lanes' missiles as a caller edited them)
+  // (the episode accumulators, the sticky overflow count and the sampler's tick stay: an abandoned game is no finished episode)
+  HIP_TRY(sf_launch_reset_lanes(b->args, mask_dev, image ? nullptr : obs_dev, (hipStream_t)stream));
+  b->draw_current = false;
+  if (b->args.draw && b->render_ready) {  // an image batch: its draw records follow the state at once (sf_drawrec_kernel)
+    SfKernelArgs da = b->args;
+    da.draw_pics = b->d_xcache ? 1 : 0;
+    HIP_TRY(sf_launch_drawrec(da, (hipStream_t)stream));
+    b->draw_current = true;
+  }
+  if (image && obs_dev) return render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
+  return SF_OK;
+}
+
 // One step launch as an entry point asks for it: what sf_step, sf_step_record, sf_rollout, ... differ in.
 struct StepLaunch {
   const char* who;                // the entry point's name in error texts

@@ -134,7 +134,18 @@ __global__ __launch_bounds__(256) void sf_eplog_apply_kernel(SfEplogArgs a, cons
   if (live) a.acc[e] = acc;
 }
 
+// sf_eplog_restart_where: the marked envs' running accumulators start over; nothing else of the log is touched
+__global__ __launch_bounds__(256) void sf_eplog_restart_where_kernel(int4* __restrict__ acc, const uint8_t* __restrict__ mask, int n) {
+  const int e = blockIdx.x * kTile + (int)threadIdx.x;
+  if (e < n && mask[e] != 0) acc[e] = make_int4(0, 0, 0, 0);
+}
+
 }  // namespace
+
+hipError_t sf_launch_eplog_restart_where(const SfEplogArgs& a, const uint8_t* mask, hipStream_t stream) {
+  hipLaunchKernelGGL(sf_eplog_restart_where_kernel, dim3((unsigned)((a.n + kTile - 1) / kTile)), dim3(256), 0, stream, a.acc, mask, a.n);
+  return hipGetLastError();
+}
 
 hipError_t sf_launch_eplog_update(const SfEplogArgs& a, const int32_t* rew, const uint8_t* done, const uint8_t* info,
                                   const void* actions, int act_type, int K, hipStream_t stream) {

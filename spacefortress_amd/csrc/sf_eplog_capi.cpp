@@ -125,6 +125,16 @@ extern "C" int sf_eplog_restart(sf_eplog* h, void* stream) {
   return SF_OK;
 }
 
+extern "C" int sf_eplog_restart_where(sf_eplog* h, const uint8_t* mask_dev, void* stream) {
+  if (!h || !mask_dev) {
+    sf_set_error("sf_eplog_restart_where: null log or mask");
+    return SF_ERR_ARG;
+  }
+  DeviceGuard guard(h->device);
+  HIP_TRY(sf_launch_eplog_restart_where(h->a, mask_dev, (hipStream_t)stream));
+  return SF_OK;
+}
+
 extern "C" int sf_eplog_clear(sf_eplog* h, void* stream) {
   if (!h) {
     sf_set_error("sf_eplog_clear: null log");

@@ -6,10 +6,13 @@
 #include "sf_glyphs.h"
 #include "sf_layout.h"
 #include "sfmi.h"
+#include "sfmi_masked.h"
 
 // sf_kernels.hip
 hipError_t sf_launch_reset(const SfKernelArgs& a, int first, unsigned cursor0, unsigned stride, void* obs,
                            hipStream_t stream);
+// env.reset() in the envs whose byte of mask [n_envs] is not zero (sfmi.h: sf_reset_lanes); obs may be null
+hipError_t sf_launch_reset_lanes(const SfKernelArgs& a, const uint8_t* mask, void* obs, hipStream_t stream);
 hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, const void* actions, int act_type, void* obs,
                           int32_t* reward, uint8_t* done, uint8_t* info, int n_steps, bool fused, hipStream_t stream);
 
@@ -98,6 +101,8 @@ struct SfEplogArgs {
 };
 hipError_t sf_launch_eplog_update(const SfEplogArgs& a, const int32_t* rew, const uint8_t* done, const uint8_t* info,
                                   const void* actions, int act_type, int K, hipStream_t stream);
+// zero the four running accumulators of the envs whose byte of mask [n] is not zero
+hipError_t sf_launch_eplog_restart_where(const SfEplogArgs& a, const uint8_t* mask, hipStream_t stream);
 
 // sf_host.cpp (no HIP calls: usable and tested without a GPU)
 void sf_host_fill_consts(const sf_preset& p, double* consts /* SF_CONST_DOUBLES */);

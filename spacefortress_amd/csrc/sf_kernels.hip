@@ -801,6 +801,80 @@ __global__ __launch_bounds__(SF_BLOCK) void sf_reset_kernel(SfKernelArgs a, int 
 }
 
 // ---------------------------------------------------------------------------------------------
+// sf_reset_lanes: env.reset() in the envs the caller marks (ENV:163-178), the others play on.  One wave per tile, a lane
+// per env; mask = uint8 [n_envs], any non-zero byte marks its env (no byte at or beyond n_envs is read).  A tile without a
+// marked env returns before it writes anything.  Otherwise the marked lanes start a new game exactly as sf_reset_kernel's
+// re-reset does -- prev_vlner and the spawn cursor are the lane's own --, and their missiles leave the tile's pool: the
+// kept lanes' entries go through LDS by (owner, slot) and the pool is rebuilt slot by slot with ballot + prefix count,
+// the order sf_slots_to_mpool_kernel and sf_lanes_load_kernel give; the new count goes into every lane's missile word.
+// A kept lane's chunks, shells and slots are as before (only WHERE its entries sit in the pool may differ, which no row
+// and no tick can tell); the lanes behind the batch in a partial last tile count as kept.  obs (may be null): the marked
+// lanes' rows as sf_reset_kernel writes them; no other row is touched.  hint (image batches): the marked lanes' bits are
+// cleared -- a new game's ship did not die in the last tick.
+__global__ __launch_bounds__(64) void sf_reset_lanes_kernel(SfKernelArgs a, const uint8_t* mask, void* obs) {
+  __shared__ d2_t spos[64][SF_NSLOT];
+  __shared__ unsigned short sang[64][SF_NSLOT];
+  const unsigned lane = threadIdx.x;
+  const long tile_i = blockIdx.x;
+  const long e = tile_i * 64 + lane;
+  const bool marked = e < a.n_envs && mask[e] != 0;
+  const unsigned long long rmask = __ballot(marked);
+  if (rmask == 0ull) return;  // (uniform)
+  unsigned char* const tb = a.state + (size_t)tile_i * sfl::kTileBytes;
+  const Off o = {lane * 16u, lane * 8u, lane * 4u, lane * 2u, lane};
+  // everything that is read from the tile, first
+  const i4_t mi = SF_LD(i4_t, SF_CHUNK(misc, 0), o.o16);
+  const unsigned pvl_w = SF_LD(unsigned, SF_CHUNK(timers_a, 0), o.o16);
+  const unsigned n_pool = (unsigned)__builtin_amdgcn_readfirstlane(mi.z) >> SF_MPOOL_SHIFT;  // (the same in every lane of the tile)
+  for (unsigned i = lane; i < n_pool && i < 64u * SF_NSLOT; i += 64) {  // (the pool holds 64 * SF_NSLOT entries)
+    const unsigned m = SF_LD(unsigned, SF_CHUNK(missile_meta, 0), i * 4u);
+    const unsigned ow = SF_MM_OWNER(m);
+    if (!((rmask >> ow) & 1ull) && SF_MM_SLOT(m) < (unsigned)SF_NSLOT) {  // (a slot tag is below SF_NSLOT; the LDS rows hold no more)
+      spos[ow][SF_MM_SLOT(m)] = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), i * 16u);
+      sang[ow][SF_MM_SLOT(m)] = (unsigned short)SF_MM_ANGLE(m);
+    }
+  }
+  const unsigned kept = marked ? 0u : ((unsigned)mi.z & SF_MASK_LOW);
+  __syncthreads();
+  // the pool, slot by slot (sf_slots_to_mpool_kernel's order)
+  unsigned wp = 0;
+  for (int s = 0; s < SF_NSLOT; s++) {
+    const bool live = (kept >> s) & 1u;
+    const unsigned long long b = __ballot(live);
+    const unsigned idx = wp + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+    wp += (unsigned)__popcll(b);
+    if (live) {
+      *reinterpret_cast<d2_t*>(SF_CHUNK(missile_pos, 0) + (size_t)idx * 16) = spos[lane][s];
+      *reinterpret_cast<unsigned*>(SF_CHUNK(missile_meta, 0) + (size_t)idx * 4) = SF_MM_PACK(sang[lane][s] & 511u, lane, s);
+    }
+  }
+  if (!marked) {
+    *reinterpret_cast<unsigned*>(SF_CHUNK(misc, 0) + o.o16 + 8u) = kept | (wp << SF_MPOOL_SHIFT);
+  } else {
+    Lane L;
+    L.prev_vlner = (int)(pvl_w & 0xFFFu);
+    L.cursor = (unsigned)mi.y;
+    new_game(a, L);
+    L.mpool = wp;
+    store_lane(tb, o, L);
+    if (obs != nullptr && a.obs_type != 3) {  // (sf_reset_kernel's observation of a new game)
+      Extras x = compute_extras(a, L, sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x), sf_atan2<false>(L.vy, L.vx));
+      if (a.ref_reset_obs) x = Extras{0.0, 0.0, 0.0};
+      if (a.obs_f64)
+        write_obs<double>(a, (double*)obs + (size_t)e * a.obs_dim, L, x);
+      else
+        write_obs<float>(a, (float*)obs + (size_t)e * a.obs_dim, L, x);
+    }
+  }
+  if (a.hint && lane == 0) a.hint[tile_i] &= ~rmask;
+}
+
+hipError_t sf_launch_reset_lanes(const SfKernelArgs& a, const uint8_t* mask, void* obs, hipStream_t stream) {
+  hipLaunchKernelGGL(sf_reset_lanes_kernel, dim3((unsigned)((a.n_envs + 63) / 64)), dim3(64), 0, stream, a, mask, obs);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // FUSED = false: one tick per launch (sf_step, the VecEnv.step path).
 // FUSED = true:  n_steps ticks per launch with the actions of all of them given up front
 // (sf_rollout): the wave keeps its state in registers between ticks, so a tick costs neither the

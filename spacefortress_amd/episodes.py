@@ -91,6 +91,16 @@ class EpisodeLog:
         lanes).  Finished records and the histogram stay."""
         _lib.check(self._L.sf_eplog_restart(self._h, self._stream()))
 
+    def restart_where(self, mask):
+        """`restart` for the envs whose byte of `mask` (uint8 or bool [N] on this device) is not zero: SFVecEnv.reset_lanes.
+        The other envs' running sums go on; no record, no histogram count.  Stream work: nothing synchronises."""
+        if torch.is_tensor(mask) and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if not (torch.is_tensor(mask) and mask.dtype == torch.uint8 and mask.device == self.device and mask.dim() == 1
+                and mask.numel() == self.n_envs and mask.is_contiguous()):
+            raise ValueError("mask must be a contiguous uint8 or bool tensor [%d] on %s" % (self.n_envs, self.device))
+        _lib.check(self._L.sf_eplog_restart_where(self._h, C.c_void_p(mask.data_ptr()), self._stream()))
+
     def clear(self):
         """Zero everything: accumulators, ring, histogram, `total` and the row count."""
         _lib.check(self._L.sf_eplog_clear(self._h, self._stream()))

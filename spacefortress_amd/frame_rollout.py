@@ -81,7 +81,7 @@ class FrameRollout(DeviceRollout):
         if name == "observations":
             raise AttributeError("FrameRollout keeps every frame once and has no `observations` tensor: "
                                  "stack_at(t) is what observations[t] holds in the stacked storage")
-        raise AttributeError(name)
+        return super().__getattr__(name)
 
     def nbytes(self):
         """Bytes of observation storage held on the device: the frames and their start flags."""

@@ -27,6 +27,11 @@ class FrameStack:
         self._done = torch.empty(n, dtype=torch.uint8, device=env.device)
         self._info = torch.empty(n, dtype=torch.uint8, device=env.device)
 
+    def __getattr__(self, name):
+        if name == "reset_lanes":  # (not forwarded to the env: see _lib.NO_RESET_LANES)
+            raise AttributeError(_lib.NO_RESET_LANES % type(self).__name__)
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+
     def _slot(self, k):
         return self.ring[:, k:k + 1]  # [N, 1, 84, 84] view, env stride = num_stack frames
 

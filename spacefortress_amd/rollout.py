@@ -54,6 +54,11 @@ class DeviceRollout:
         self._info = torch.empty(n, dtype=torch.uint8, device=dev)
         self._ptr = None
 
+    def __getattr__(self, name):
+        if name == "reset_lanes":  # (not forwarded to the env: see _lib.NO_RESET_LANES)
+            raise AttributeError(_lib.NO_RESET_LANES % type(self).__name__)
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+
     def _alloc_observations(self, shape):
         self.observations = torch.zeros(shape, dtype=self.env.obs_dtype, device=self.env.device)
 

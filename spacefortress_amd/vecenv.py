@@ -132,6 +132,62 @@ class SFVecEnv:
         _lib.check(self._L.sf_reset(self._h, C.c_void_p(obs.data_ptr()), self._stream()))
         return obs.cpu().numpy() if numpy else obs
 
+    def _lane_mask(self, lanes, mask):
+        """The uint8 [N] device mask of reset_lanes from exactly one of `lanes` (indices) or `mask` (used as it is)."""
+        n = self.num_envs
+        if (lanes is None) == (mask is None):
+            raise ValueError("reset_lanes: give exactly one of `lanes` and `mask`")
+        if mask is not None:
+            if not (torch.is_tensor(mask) and mask.dtype in (torch.uint8, torch.bool) and mask.device == self.device
+                    and mask.dim() == 1 and mask.numel() == n and mask.is_contiguous()):
+                raise ValueError("reset_lanes: mask must be a contiguous uint8 or bool tensor [%d] on %s" % (n, self.device))
+            return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        if torch.is_tensor(lanes):
+            if lanes.dtype not in (torch.int32, torch.int64):
+                raise ValueError("reset_lanes: lanes must be int32 or int64 indices (got %s)" % (lanes.dtype,))
+            idx = lanes.reshape(-1).to(self.device, torch.int64)
+        else:
+            a = np.asarray(lanes)
+            if a.size and a.dtype.kind not in "iu":
+                raise ValueError("reset_lanes: lanes must be integer indices (got %s)" % (a.dtype,))
+            idx = torch.from_numpy(np.ascontiguousarray(a.reshape(-1), np.int64)).to(self.device)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):  # (synchronises; the mask form does not)
+            raise ValueError("reset_lanes: lane index outside [0, %d)" % n)
+        m = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        m[idx] = 1
+        return m
+
+    def reset_lanes(self, lanes=None, mask=None, out=None):
+        """env.reset() in the chosen lanes only (ENV:163-178; sfmi.h: sf_reset_lanes): new games there -- the next entry of the
+        lane's own spawn stream, prev_vlner kept --, every other lane plays on untouched.  Exactly one of `lanes` (an index
+        list or tensor, turned into a mask on the device; checked against the batch, which synchronises) or `mask` (uint8 or
+        bool device tensor [N], any non-zero byte; used as it is: nothing synchronises, graph capture works with `out`).
+        Returns the observation buffer, `out` or the env's own: for features only the reset rows are written; image batches
+        get every lane's frame of its current state.  Not a finished episode: episode_stats() and check_state() do not
+        change.  A recording is dropped (RuntimeError) as with reset(), the duration log starts over and an enabled episode
+        log starts the reset lanes' running sums over."""
+        m = self._lane_mask(lanes, mask)
+        if out is None:
+            obs = self._alloc()[0]
+        else:
+            obs = out
+            if not (torch.is_tensor(obs) and obs.device == self.device and obs.dtype == self.obs_dtype and obs.is_contiguous()
+                    and tuple(obs.shape) == (self.num_envs,) + tuple(self.obs_shape)):
+                raise ValueError("reset_lanes: out must be a contiguous %s tensor %s on %s"
+                                 % (self.obs_dtype, (self.num_envs,) + tuple(self.obs_shape), self.device))
+        # _touch() with the episode log following the mask: the other lanes' running sums go on
+        self._fresh = False
+        if self._durations is not None:
+            self._durations.reset()
+        if self._episodes is not None:
+            self._episodes.restart_where(m)
+        if self._rec is not None:
+            self._rec = None
+            raise RuntimeError("reset_lanes() during a recording: a replay file cannot express a manual reset; "
+                               "the recording was dropped")
+        _lib.check(self._L.sf_reset_lanes(self._h, C.c_void_p(m.data_ptr()), C.c_void_p(obs.data_ptr()), self._stream()))
+        return obs
+
     def step_tensors(self, actions, out=None):
         """Device fast path: `actions` is a contiguous uint8/int32/int64 tensor on this device.
         Returns (obs, reward int32, done uint8, info uint8) tensors; nothing synchronises."""

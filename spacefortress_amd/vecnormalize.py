@@ -50,6 +50,11 @@ class SFVecNormalize:
         self._rew = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
         self._pending = None
 
+    def __getattr__(self, name):
+        if name == "reset_lanes":  # (not forwarded to the env: see _lib.NO_RESET_LANES)
+            raise AttributeError(_lib.NO_RESET_LANES % type(self).__name__)
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+
     def _stream(self):
         return _lib.raw_stream(self.device)
 
