@@ -280,18 +280,28 @@ int sf_render_view(sf_batch* b, const sf_view* view, int first_lane, int n_lanes
 int sf_view_circle_segments(double xx, double yx, double xy, double yy, double radius);
 
 /* One step of the trainer's frame stack in one launch (rl/train.py:51-56,92-97): the 84x84 frame of every env
- * goes to slot `slot` of stack_dev uint8 [n_envs][num_stack][84][84] (16-byte aligned), and an env whose
- * done_dev flag is set (may be NULL) first gets its other slots zeroed. */
+ * goes to slot `slot` of stack_dev uint8 [n_envs][num_stack][84][84], and an env whose done_dev flag is set
+ * (any non-zero byte; done_dev may be NULL) first gets its other slots zeroed; nothing else is touched.
+ * stack_dev must be 16-byte aligned: always in the default geometry, and in any other geometry whenever
+ * done_dev is given (there the finished envs' slots are zeroed in 16-byte pieces by a launch of their own;
+ * without done_dev 4 bytes are enough).  SF_ERR_ARG, with nothing launched, for a stack that is not, for
+ * num_stack < 1 and for a slot outside 0 .. num_stack-1. */
 int sf_render_stack(sf_batch* b, uint8_t* stack_dev, int num_stack, int slot, const uint8_t* done_dev, void* stream);
 
 /* The same update from one buffer into ANOTHER (the trainer stores the stacked observation of every step,
  * rollouts.observations[step + 1], rl/train.py:98): frames 1 .. num_stack-1 of prev_stack_dev become frames
- * 0 .. num_stack-2 of stack_dev (zeros for an env whose done flag is set), the new frame goes last. */
+ * 0 .. num_stack-2 of stack_dev (zeros for an env whose done flag is set), the new frame goes last;
+ * prev_stack_dev is only read.  Default geometry only.  Both stacks 16-byte aligned, and the byte ranges
+ * [prev_stack_dev, + n_envs * num_stack * 7056) and [stack_dev, + the same) must not intersect (one env's
+ * workgroup would overwrite what another still reads): they may touch, as consecutive steps of one storage
+ * do.  SF_ERR_ARG, with nothing launched, otherwise. */
 int sf_render_shift(sf_batch* b, const uint8_t* prev_stack_dev, uint8_t* stack_dev, int num_stack, const uint8_t* done_dev,
                     void* stream);
 
 /* `current_obs *= masks` of the trainer's frame stack (rl/train.py:92-93): zero the bytes_per_env bytes of
- * every env whose done flag is set, touching nothing else.  stack_dev uint8 [n_envs][bytes_per_env]. */
+ * every env whose done flag is set (any non-zero byte), touching nothing else.  stack_dev uint8
+ * [n_envs][bytes_per_env], 16-byte aligned, bytes_per_env a multiple of 16; SF_ERR_ARG, with nothing
+ * launched, otherwise and for n_envs <= 0 or a null pointer. */
 int sf_frame_stack_clear(uint8_t* stack_dev, size_t bytes_per_env, const uint8_t* done_dev, int n_envs, void* stream);
 
 /* ---- telemetry: what happened in a tick, per env, as a bitmask -- the reference's per-tick event strings

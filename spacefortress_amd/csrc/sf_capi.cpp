@@ -696,6 +696,11 @@ static int render(sf_batch* b, int mode, uint8_t* frames_dev, size_t env_stride,
       sf_set_error("image frames of a non-default geometry must be 4-byte aligned and env_stride a multiple of 4");
       return SF_ERR_ARG;
     }
+    // (sf_stack_clear_kernel zeroes a finished env's stack in 16-byte pieces, from the stack's own start)
+    if (stack_done && (((uintptr_t)frames_dev - (size_t)stack_slot * frame) & 15) != 0) {
+      sf_set_error("sf_render_stack: a stack with done flags must be 16-byte aligned");
+      return SF_ERR_ARG;
+    }
     SF_FLUSH_VIEW(b, stream);
     if (stack_done)  // `current_obs *= masks` for the finished envs, then the new frame into its slot
       HIP_TRY(sf_launch_stack_clear(frames_dev - (size_t)stack_slot * frame, (size_t)stack_n * frame, stack_done, b->n_envs, stream));
@@ -786,13 +791,22 @@ extern "C" int sf_render_stack(sf_batch* b, uint8_t* stack_dev, int num_stack, i
 
 extern "C" int sf_render_shift(sf_batch* b, const uint8_t* prev_stack_dev, uint8_t* stack_dev, int num_stack,
                                const uint8_t* done_dev, void* stream) {
-  if (!b || !prev_stack_dev || !stack_dev || num_stack < 1 || prev_stack_dev == stack_dev ||
-      ((uintptr_t)prev_stack_dev & 15) != 0) {
-    sf_set_error("sf_render_shift: need a batch and two different 16-byte aligned stacks");
+  if (!b || !prev_stack_dev || !stack_dev || num_stack < 1 || ((uintptr_t)prev_stack_dev & 15) != 0) {
+    sf_set_error("sf_render_shift: need a batch and two 16-byte aligned stacks");
     return SF_ERR_ARG;
   }
-  DeviceGuard guard(b->device);
   const size_t frame = (size_t)SF_OUT * SF_OUT;
+  {
+    // an env's workgroup reads its own frames of the previous stack while others write theirs of the new one: the two
+    // may touch (consecutive steps of a rollout's storage) but share no byte
+    const uintptr_t p0 = (uintptr_t)prev_stack_dev, s0 = (uintptr_t)stack_dev;
+    const size_t bytes = (size_t)b->n_envs * (size_t)num_stack * frame;
+    if (p0 < s0 + bytes && s0 < p0 + bytes) {
+      sf_set_error("sf_render_shift: the previous stack and the new one overlap");
+      return SF_ERR_ARG;
+    }
+  }
+  DeviceGuard guard(b->device);
   return render(b, SF_OBS_IMAGE, stack_dev + (size_t)(num_stack - 1) * frame, (size_t)num_stack * frame, (hipStream_t)stream,
                 done_dev, num_stack - 1, num_stack, prev_stack_dev);
 }
