@@ -1,6 +1,6 @@
 // sf_capi.cpp -- the C ABI of include/sfmi.h: batch lifecycle, step/reset launches, state access.
-// Host code only; the kernels are in sf_kernels.hip.  There is no CPU implementation of the
-// path in this library: every entry point that computes needs a HIP device.
+// Host code only; the kernels are in sf_kernels.hip (reset, step) and sf_state_ops.hip (the state tools).  There is no CPU
+// implementation of the path in this library: every entry point that computes needs a HIP device.
 #include <limits.h>
 #include <math.h>
 #include <stdio.h>
@@ -98,6 +98,8 @@ namespace {
     }                                                                                  \
   } while (0)
 
+#define SF_TRY(expr) do { const int rc_ = (expr); if (rc_ != SF_OK) return rc_; } while (0) /* ... for a call that returns an SF_* code */
+
 // keep the caller's (PyTorch's) current device untouched
 struct DeviceGuard {
   int prev = -1;
@@ -118,11 +120,7 @@ int flush_missile_view(sf_batch* b, hipStream_t stream) {
   b->draw_current = false;
   return SF_OK;
 }
-#define SF_FLUSH_VIEW(b, stream)                                   \
-  do {                                                             \
-    int rc_ = flush_missile_view((b), (hipStream_t)(stream));      \
-    if (rc_ != SF_OK) return rc_;                                  \
-  } while (0)
+#define SF_FLUSH_VIEW(b, stream) SF_TRY(flush_missile_view((b), (hipStream_t)(stream)))
 
 const unsigned long long kAccInit[SF_ACC_WORDS] = {
     0, 0, 0, 0, 0, 0, (unsigned long long)LLONG_MAX, (unsigned long long)LLONG_MIN, 0, 0, 0};
@@ -145,6 +143,32 @@ int write_action_records(sf_batch* b, uint64_t seed, uint32_t first_lane, hipStr
 
 bool is_pow2(long v) { return v > 0 && (v & (v - 1)) == 0; }
 
+// b->d_xcache behind the envs' explosion cache (n_envs * SF_XC_BYTES), as byte offsets: the 36 fortress pictures, the destroyed
+// fortress's explosion (in the layout of an env's cache entry), the score / bar pictures; and the whole allocation's size
+struct PictureTail { size_t fort, destroyed, hud, total; };
+PictureTail picture_tail(const sf_batch* b) {
+  const size_t fort = (size_t)b->n_envs * SF_XC_BYTES, destroyed = fort + 36 * SF_FP_BYTES, hud = destroyed + SF_XC_BYTES;
+  return {fort, destroyed, hud, hud + SF_HUD_BYTES};
+}
+// ... and the pictures drawn into the (zeroed) tail, by the frame kernel's own code
+int draw_pictures(sf_batch* b, hipStream_t stream) {
+  const PictureTail t = picture_tail(b);
+  HIP_TRY(sf_launch_hud_pictures(b->d_bg, b->d_bg84, b->d_tabs, b->d_xcache + t.hud, b->d_glyphs, stream));
+  HIP_TRY(sf_launch_fort_patches(b->d_bg, b->d_bg84, b->d_tabs, b->d_xcache + t.fort, b->d_arcs, b->d_falpha, stream));
+  return SF_OK;
+}
+
+// The envs' draw records from the state as it is (sf_drawrec_kernel), into b->d_draw, which exists.  Current afterwards for an
+// image batch, whose step launches keep them so; a batch that steps with a symbolic observation rebuilds before every frame.
+int rebuild_draw_records(sf_batch* b, hipStream_t stream) {
+  SfKernelArgs da = b->args;
+  da.draw = b->d_draw;
+  da.draw_pics = b->d_xcache ? 1 : 0;
+  HIP_TRY(sf_launch_drawrec(da, stream));
+  b->draw_current = b->args.draw != nullptr;
+  return SF_OK;
+}
+
 // What a batch needs to draw frames, made once: the per-env explosion cache followed by the 36 fortress pictures, the
 // destroyed fortress's explosion (in the layout of an env's cache entry) and the score / bar pictures -- all drawn here, on
 // `stream`, by the frame kernel's own code; the 36 x 4 backgrounds with the fortress in them; the envs' draw records.
@@ -159,11 +183,10 @@ int ensure_render_resources(sf_batch* b, hipStream_t stream) {
     HIP_TRY(hipMemsetAsync(b->d_draw, 0, bytes, stream));
   }
   if (!b->d_xcache && !getenv("SFMI_NO_EXPLOSION_CACHE")) {
-    const size_t bytes = (size_t)b->n_envs * SF_XC_BYTES, tail = 36 * SF_FP_BYTES + SF_XC_BYTES + SF_HUD_BYTES;
-    HIP_TRY(hipMalloc((void**)&b->d_xcache, bytes + tail));
-    HIP_TRY(hipMemsetAsync(b->d_xcache, 0, bytes + tail, stream));
-    HIP_TRY(sf_launch_hud_pictures(b->d_bg, b->d_bg84, b->d_tabs, b->d_xcache + bytes + 36 * SF_FP_BYTES + SF_XC_BYTES, b->d_glyphs, stream));
-    HIP_TRY(sf_launch_fort_patches(b->d_bg, b->d_bg84, b->d_tabs, b->d_xcache + bytes, b->d_arcs, b->d_falpha, stream));
+    const size_t total = picture_tail(b).total;
+    HIP_TRY(hipMalloc((void**)&b->d_xcache, total));
+    HIP_TRY(hipMemsetAsync(b->d_xcache, 0, total, stream));
+    SF_TRY(draw_pictures(b, stream));
   }
   HIP_TRY(hipStreamSynchronize(stream));
   b->render_ready = true;
@@ -187,10 +210,8 @@ int bake_default_glyphs(sf_batch* b) {
   HIP_TRY(hipMemcpy(b->d_glyphs, &b->h_glyphs, sizeof(SfGlyphAtlas), hipMemcpyHostToDevice));
   b->baked_glyphs = b->h_glyphs;
   if (b->render_ready && b->d_xcache) {
-    const size_t bytes = (size_t)b->n_envs * SF_XC_BYTES, tail = 36 * SF_FP_BYTES + SF_XC_BYTES + SF_HUD_BYTES;
-    HIP_TRY(hipMemset(b->d_xcache, 0, bytes + tail));
-    HIP_TRY(sf_launch_hud_pictures(b->d_bg, b->d_bg84, b->d_tabs, b->d_xcache + bytes + 36 * SF_FP_BYTES + SF_XC_BYTES, b->d_glyphs, nullptr));
-    HIP_TRY(sf_launch_fort_patches(b->d_bg, b->d_bg84, b->d_tabs, b->d_xcache + bytes, b->d_arcs, b->d_falpha, nullptr));
+    HIP_TRY(hipMemset(b->d_xcache, 0, picture_tail(b).total));
+    SF_TRY(draw_pictures(b, nullptr));
     HIP_TRY(hipDeviceSynchronize());
   }
   b->draw_current = false;
@@ -715,23 +736,16 @@ static int render(sf_batch* b, int mode, uint8_t* frames_dev, size_t env_stride,
     return SF_ERR_ARG;
   }
   SF_FLUSH_VIEW(b, stream);
-  {
-    // first frame of a batch that steps with a symbolic observation: the caches, pictures and draw records (feature-only
-    // batches never pay for them; image batches made them in sf_create)
-    const int rc = ensure_render_resources(b, stream);
-    if (rc != SF_OK) return rc;
-  }
-  if (!b->draw_current) {  // the state changed otherwise than through a step launch of an image batch: records from the state
-    SfKernelArgs da = b->args;
-    da.draw = b->d_draw;
-    da.draw_pics = b->d_xcache ? 1 : 0;
-    HIP_TRY(sf_launch_drawrec(da, stream));
-    b->draw_current = b->args.draw != nullptr;  // (only an image batch's step launches keep them current from here on)
-  }
-  const unsigned char* fpatch = b->d_xcache ? b->d_xcache + (size_t)b->n_envs * SF_XC_BYTES : nullptr;
+  // first frame of a batch that steps with a symbolic observation: the caches, pictures and draw records (feature-only
+  // batches never pay for them; image batches made them in sf_create)
+  SF_TRY(ensure_render_resources(b, stream));
+  // the state changed otherwise than through a step launch of an image batch: records from the state
+  if (!b->draw_current) SF_TRY(rebuild_draw_records(b, stream));
+  const PictureTail tail = picture_tail(b);
+  const unsigned char* fpatch = b->d_xcache ? b->d_xcache + tail.fort : nullptr;
   HIP_TRY(sf_launch_render(b->d_state, b->d_draw, b->n_envs, b->d_bg, b->d_bg84, b->d_tabs, frames_dev, env_stride, b->d_xcache, fpatch,
                            mode == SF_OBS_IMAGE ? 1 : 0, stack_done, stack_slot, stack_n, stack_prev, b->args.hint,
-                           fpatch ? fpatch + 36 * SF_FP_BYTES + SF_XC_BYTES : nullptr, b->d_consts + SF_LDS_TRIG, b->d_arcs, b->d_falpha, b->d_glyphs, stream));
+                           b->d_xcache ? b->d_xcache + tail.hud : nullptr, b->d_consts + SF_LDS_TRIG, b->d_arcs, b->d_falpha, b->d_glyphs, stream));
   return SF_OK;
 }
 
@@ -745,13 +759,8 @@ extern "C" int sf_draw_records(sf_batch* b, void* host, size_t bytes, int from_s
   HIP_TRY(hipDeviceSynchronize());
   if (from_state) {
     SF_FLUSH_VIEW(b, nullptr);
-    const int rc = ensure_render_resources(b, nullptr);
-    if (rc != SF_OK) return rc;
-    SfKernelArgs da = b->args;
-    da.draw = b->d_draw;
-    da.draw_pics = b->d_xcache ? 1 : 0;
-    HIP_TRY(sf_launch_drawrec(da, nullptr));
-    b->draw_current = b->args.draw != nullptr;
+    SF_TRY(ensure_render_resources(b, nullptr));
+    SF_TRY(rebuild_draw_records(b, nullptr));
   } else if (!b->d_draw) {
     sf_set_error("sf_draw_records: this batch has no draw records yet (they come with its first frame)");
     return SF_ERR_ARG;
@@ -850,12 +859,8 @@ extern "C" int sf_reset_lanes(sf_batch* b, const uint8_t* mask_dev, void* obs_de
   // (the episode accumulators, the sticky overflow count and the sampler's tick stay: an abandoned game is no finished episode)
   HIP_TRY(sf_launch_reset_lanes(b->args, mask_dev, image ? nullptr : obs_dev, (hipStream_t)stream));
   b->draw_current = false;
-  if (b->args.draw && b->render_ready) {  // an image batch: its draw records follow the state at once (sf_drawrec_kernel)
-    SfKernelArgs da = b->args;
-    da.draw_pics = b->d_xcache ? 1 : 0;
-    HIP_TRY(sf_launch_drawrec(da, (hipStream_t)stream));
-    b->draw_current = true;
-  }
+  // an image batch whose resources exist: its draw records follow the state at once
+  if (b->args.draw && b->render_ready) SF_TRY(rebuild_draw_records(b, (hipStream_t)stream));
   if (image && obs_dev) return render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
   return SF_OK;
 }
@@ -1365,7 +1370,7 @@ extern "C" int sf_render_view(sf_batch* b, const sf_view* view, int first_lane, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// lane states (sfmi.h): rows of SF_LANE_STATE_BYTES <-> lanes, on the device (sf_kernels.hip: sf_lanes_*_kernel)
+// lane states (sfmi.h): rows of SF_LANE_STATE_BYTES <-> lanes, on the device (sf_state_ops.hip: sf_lanes_*_kernel)
 namespace {
 void lane_header(const sf_batch* b, uint32_t h[4]) {
   h[0] = SF_LANE_STATE_MAGIC | SF_LANE_STATE_VERSION;

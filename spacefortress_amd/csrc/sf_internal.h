@@ -8,14 +8,15 @@
 #include "sfmi.h"
 #include "sfmi_masked.h"
 
-// sf_kernels.hip
+// sf_kernels.hip: the hot path
 hipError_t sf_launch_reset(const SfKernelArgs& a, int first, unsigned cursor0, unsigned stride, void* obs,
                            hipStream_t stream);
-// env.reset() in the envs whose byte of mask [n_envs] is not zero (sfmi.h: sf_reset_lanes); obs may be null
-hipError_t sf_launch_reset_lanes(const SfKernelArgs& a, const uint8_t* mask, void* obs, hipStream_t stream);
 hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, const void* actions, int act_type, void* obs,
                           int32_t* reward, uint8_t* done, uint8_t* info, int n_steps, bool fused, hipStream_t stream);
 
+// sf_state_ops.hip: the state tools
+// env.reset() in the envs whose byte of mask [n_envs] is not zero (sfmi.h: sf_reset_lanes); obs may be null
+hipError_t sf_launch_reset_lanes(const SfKernelArgs& a, const uint8_t* mask, void* obs, hipStream_t stream);
 // the envs' draw records (sf_drawrec.h) from the state as it is: a.draw / a.draw_pics say where and for which pictures
 hipError_t sf_launch_drawrec(const SfKernelArgs& a, hipStream_t stream);
 

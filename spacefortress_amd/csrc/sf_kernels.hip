@@ -1,4 +1,5 @@
-// sf_kernels.hip -- the env.step() hot path as HIP kernels for gfx950 (MI355X, CDNA4).
+// sf_kernels.hip -- the env.step() hot path as HIP kernels for gfx950 (MI355X, CDNA4): sf_reset_kernel, sf_step_kernel, their
+// launchers.  The state tools are in sf_state_ops.hip, what both share in sf_lane_dev.h.
 //
 // One lane per environment.  A launch of sf_step_kernel advances every env of the
 // batch by one 34 ms tick and does, fused, what the reference spreads over three
@@ -50,10 +51,8 @@
 #include <cstdlib>
 #include <stdint.h>
 
-#include "sf_internal.h"
-#include "sf_layout.h"
-#include "sf_deg_dd.h"
 #include "sf_drawrec.h"
+#include "sf_lane_dev.h"  // (with sf_internal.h and sf_layout.h)
 
 // ---- the build's switches: numeric tunables that name a real quantity, and one instrument (SF_STAMPS) ----
 // Four waves per workgroup share one LDS copy of the cos/sin table (one barrier, early, while the
@@ -80,11 +79,6 @@
 // through which the missile pool's entries tell their owner lanes what happened to them; then the observation staging
 #define SF_LDS_EV SF_LDS_DOUBLES
 /* then (sf_step_kernel: kLdsAtab, kLdsStage) behind the BLK event words: atan(k / 16), k = 0..16 (sf_atan2_core), and the staging rows */
-#define SF_MAX_MISSILES_D 20.0 /* sf.MAX_MISSILES / sf.MAX_SHELLS as divisors (ENV:124-125) */
-
-#ifndef M_PI
-#define M_PI 3.14159265358979323846
-#endif
 
 // Diagnostic build only (-DSF_STAMPS, tools/stamps.py): shader-clock stamps at phase boundaries,
 // with forced waits so each phase owns its memory latency.  The product build has none of it.
@@ -101,91 +95,11 @@
 #define SF_STAMP(k, drain)
 #endif
 
-// Field access inside the wave's tile (sf_layout.h): `tb` is the tile base -- wave-uniform, one
-// SGPR pair for the whole state -- the group/slot offset is a compile-time constant and the lane
-// contributes a 32-bit byte offset (one VGPR per chunk size: 16, 8, 4 or 2 bytes).
-#define SF_CHUNK(group, s)                                   \
-  (tb + sfl::chunk_offset(SF_G_##group, 0) +                 \
-   (size_t)(s) * (size_t)(sfl::kGroups[SF_G_##group].chunk * sfl::kTileLanes))
-#define SF_LD(T, base, off) (*reinterpret_cast<const T*>((base) + (off)))
 #define SF_COS(ang) trig[2 * (ang)]
 #define SF_SIN(ang) trig[2 * (ang) + 1]
-// Stores of 16-byte chunks are write-through (`sc1`): the bytes leave L2 while the kernel still runs, so the
-// end-of-kernel write-back has less to flush (A/B, tools/ab.py on one device, 65 536 envs: plain stores 11.20 us per
-// launch, non-temporal 11.01, write-through 10.83.  With the earlier 1-8-byte rows `sc1` LOST 1 %: narrow
-// write-through stores are one fabric write each).  Nothing stored this way is read again inside the launch.
-// the cache bits of the write-through stores: inline-asm text and the builtins' aux value (1 = sc0, 2 = nt, 16 = sc1)
-#define SF_SC_AUX 16
-#define SF_SC_ASM "sc1"
-template <typename T>
-__device__ __forceinline__ void sf_store(T* p, T v) {
-  if constexpr (sizeof(T) == 16) {
-    // the s_nop belongs to the store: a store of more than 64 bits reads its data registers over several cycles and
-    // the next VALU write of one of them needs a wait state in between, which the compiler cannot insert for an
-    // instruction it does not see (found as misc.prev_vlner of lanes 12-15 of every 16 holding the NEXT store's word)
-    asm volatile("global_store_dwordx4 %0, %1, off " SF_SC_ASM "\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-  } else {
-    *p = v;
-  }
-}
 #define SF_ST(T, base, off, v) sf_store<T>(reinterpret_cast<T*>((base) + (off)), (T)(v))
 
-// The projectile slots, the lane's chunks and the counters go through `buffer_*` instructions on a per-wave descriptor of the
-// tile.  The slot's chunk offset (a compile-time constant too big for the 12-bit immediate) rides in
-// the scalar offset instead of costing two 64-bit VALU adds per access, and a lane that has nothing in
-// the slot gets an out-of-range offset: the hardware range check returns 0 for its load and drops its
-// store, so there is no exec-mask branch around each access.
-#define SF_GOFF(group, s) \
-  ((unsigned)sfl::chunk_offset(SF_G_##group, 0) + (unsigned)(s) * (unsigned)(sfl::kGroups[SF_G_##group].chunk * sfl::kTileLanes))
-#define SF_OOB 0x80000000u /* beyond any tile: the lane's access does not happen */
-
-typedef double d2_t __attribute__((ext_vector_type(2)));
-typedef int i4_t __attribute__((ext_vector_type(4)));
-typedef int i2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
-
-// A 128-bit buffer store with the wait state its data registers need ATTACHED.  A store of more than 64 bits reads its data
-// VGPRs over several cycles, and a VALU write of one of them in the next issue slot changes what lanes 12-15 of every 16
-// store.  The compiler inserts the s_nop for global / flat stores and for buffer stores with an immediate soffset, but takes a
-// buffer store whose soffset is an SGPR to be safe (LLVM GCNHazardRecognizer::createsVALUHazard).  On MI355X that holds
-// while the wave is alone on its SIMD -- every batch up to 65 536 envs, every test of rounds 1-3 -- and does not with two or
-// more: a batch of 262 144 envs played different games than the same envs in four batches, in exactly those lanes (round 4;
-// tests/test_gpu_parity.py::test_batches_beyond_one_wave_per_simd).  So the store goes out as inline assembly with its s_nop
-// (the compiler cannot place anything in between), like sf_store's global one; tools/store_hazard_scan.py checks a build's
-// assembly for wide buffer stores the compiler emitted bare.  AUX as the builtin's: 0 plain, 16 write-through (sc1).
-template <int AUX>
-__device__ __forceinline__ void sf_buf_st128(u4_t v, __amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
-  static_assert(AUX == 0 || AUX == 16 || AUX == 1 || AUX == 17, "cache bits of the store");
-  if constexpr (AUX == 16)
-    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen sc1\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  else if constexpr (AUX == 1)
-    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen sc0\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  else if constexpr (AUX == 17)
-    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen sc0 sc1\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  else
-    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
-
 namespace {
-
-struct Lane {
-  double sx, sy, vx, vy;
-  int angle;
-  unsigned fl;
-  int death_t, fire_t, thrust_t, left_t, right_t;
-  int fort_t, fort_death_t, fort_vuln_t;
-  int fort_angle, fort_last;
-  float points, raw;
-  int vlner, time;
-  int prev_vlner;
-  unsigned cursor, mmask, smask;
-  unsigned kc0, kc1;  // key-press counters: shots | thrusts << 16, lefts | rights << 16 (sf_layout.h: SF_KEYCOUNT_BYTE)
-  // the per-episode counters that ride above the timers, vlner, time and the cursor (sf_layout.h: SF_W_*)
-  int ep_return;
-  unsigned c_resets, c_missed, c_incs, c_maxv, c_big, c_small, c_shell, c_destroyed;
-  unsigned mpool;     // live entries of the tile's missile pool (wave-uniform; rides above the missile mask)
-  unsigned ep_kills;  // sum of info over the episode (rides above the shell mask)
-};
 
 // What one tick adds to the statistics (SRC/game.hh:29-43); flushed with atomics.
 // (Named scalars, not an array: the compiler merges `if (c) d[5]++; else d[4]++;` into a
@@ -195,111 +109,6 @@ struct StatDelta {
       missed = 0, shots = 0, thrusts = 0, lefts = 0, rights = 0, vlner_incs = 0;
   int max_vlner = 0;  // candidate for counter 12 (a running maximum)
 };
-
-struct Off {  // 32-bit byte offsets of this lane into rows of 16-, 8-, 4-, 2- and 1-byte chunks
-  unsigned o16, o8, o4, o2, o1;
-};
-
-// a / C for a compile-time constant C, bit-identical to the IEEE division it replaces, in three dependent
-// operations instead of the eleven of the general v_div_* sequence (v_rcp_f64 included): with rc = RN(1/C),
-// q = RN(a * rc) is within an ulp of a / C, rem = a - C * q is exact in an FMA, and RN(q + rem * rc) is the
-// correctly rounded quotient (Markstein's theorem).  Checked exhaustively enough on the host for every C used
-// here -- pi, 10, 20, 80, 90, 92, 180, 360, 5294: 4e8 operands each, none differ (tests/test_div_const.py keeps a
-// smaller run of the same check).  Only the sign of a zero quotient can differ (-0.0 / C gives +0.0 here); nothing
-// downstream looks at it.  The operands are angles, pixels and tick counts: no overflow, underflow or NaN.
-__device__ __forceinline__ double sf_div_const(double a, double c, double rc) {
-  const double q = a * rc;
-  const double rem = __builtin_fma(-c, q, a);
-  return __builtin_fma(rem, rc, q);
-}
-#define SF_DIV(a, C) sf_div_const((a), (double)(C), 1.0 / (double)(C))
-__device__ __forceinline__ double rad2deg(double a) { return SF_DIV(a, M_PI) * 180; }  // SRC/vector.cpp:38-40
-__device__ __forceinline__ double deg2rad(double a) { return SF_DIV(a * M_PI, 180); }  // SRC/vector.cpp:34-36
-
-// atan2 as the reference's libm rounds it where it matters.  The device libm (ocml) is faithful, glibc is correctly
-// rounded, and for nearly every argument the last-bit difference is invisible: the results only feed ceil-to-10
-// degrees (fortress sector), ceil-to-1 degree (autoturn heading) and observations.  Ships move on near-lattices,
-// though (integer spawns, velocities that are sums of 0.3 * cos(6k degrees)), and do cross x = 355 or y = 315 within
-// 1e-13: the bearing is then a whisker off +-90 or +-180 degrees -- multiples of 10 -- and which side of the
-// boundary the ROUNDED value falls on is decided by that last bit (found by a 3e8-step soak: sector 280 against the
-// reference's 270).  Next to the y axis and to the negative x axis the result is therefore formed as
-// +-pi/2 - x/y and +-pi + y/x with pi in two doubles: one rounding, the correctly rounded value, bit for bit what
-// glibc returns there (4e7 such arguments checked on the host, tests/native/atan2_axis.c).  A wave-wide test skips
-// the block on all but a handful of ticks.
-//
-// The same last bit decides whenever the bearing is within rounding noise of ANY integer degree, and in autoturn games
-// that is a regime, not an accident: a ship that thrusts at the fortress flies along an exact-degree ray.  RAZOR = 1:
-// within 1e-9 degrees of k degrees the result is formed as phi_k + N / D, N = |y| cos k - x sin k in double-double
-// (products exact by FMA; phi, cos, sin of k = 0..180 as (hi, lo) pairs, sf_deg_dd.h), D = x cos k + |y| sin k: the
-// correctly rounded value.  glibc's own atan2 is not correctly rounded in 0.08 % of such arguments (0.503-ulp errors,
-// tools/atan2_razor), so agreement there is 99.9 %, not 100 % -- against a coin toss per tick for the plain device libm.
-// atan2 for the step kernel's hot path, half the instructions of the device libm's: no special cases (the arguments are
-// finite coordinate / velocity differences), the quotient q = min / max in [0, 1] by a reciprocal and Newton steps, then
-// one table step atan(q) = atan(k / 16) + atan(t), t = (q - k/16) / (1 + q k/16), |t| <= 1/32, where five terms of the
-// series leave 3e-18.  `atab` = atan(k / 16), k = 0..16, in LDS (host libm, sf_host_fill_consts).  Within 1e-15 rad of
-// the host libm's atan2 (a few ulps; tests/native/atan2_core.c restates it on the host); everything that needs MORE than
-// that -- the axes, the integer degrees -- is decided by sf_atan2's exact forms below, which do not look at this value's
-// last bits.  (0, 0) gives a NaN: the only caller that can pass it, the velocity bearing, discards the value for a ship
-// at rest.
-__device__ __forceinline__ double sf_recip(double d) {  // 1 / d to an ulp or so, d in the normal range
-  double r = __builtin_amdgcn_rcp(d);
-  r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-  return __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-}
-__device__ __forceinline__ double sf_atan2_core(double y, double x, const double* atab) {
-  const double ax = fabs(x), ay = fabs(y);
-  const double u = __builtin_fmax(ax, ay), v = __builtin_fmin(ax, ay);
-  const double ru = sf_recip(u);
-  double q = v * ru;
-  q = __builtin_fma(__builtin_fma(-u, q, v), ru, q);
-  const double k = rint(q * 16.0), c = k * 0.0625;
-  const double den = __builtin_fma(q, c, 1.0), num = q - c;
-  const double rd = sf_recip(den);
-  double t = num * rd;
-  t = __builtin_fma(__builtin_fma(-den, t, num), rd, t);
-  const double s = t * t;
-  double p = __builtin_fma(s, 1.0 / 9.0, -1.0 / 7.0);
-  p = __builtin_fma(s, p, 0.2);
-  p = __builtin_fma(s, p, -1.0 / 3.0);
-  double a = atab[(int)k] + __builtin_fma(t, p * s, t);
-  a = ay > ax ? 1.5707963267948966 - a : a;
-  a = x < 0 ? 3.141592653589793 - a : a;
-  return copysign(a, y);
-}
-
-template <bool RAZOR>
-__device__ __forceinline__ double sf_atan2(double y, double x, const double* atab = nullptr) {
-  double r = atab ? sf_atan2_core(y, x, atab) : atan2(y, x);
-  const double ax = fabs(x), ay = fabs(y);
-  const bool ny = ax * 0x1p27 < ay;              // next to the y axis (x == 0 included)
-  const bool nx = (x < 0) & (ay * 0x1p27 < ax);  // next to the negative x axis (y == 0 included)
-  if (__ballot(ny | nx) != 0ull) {
-    if (ny | nx) {
-      const double t = ny ? x / y : y / x;
-      const double hi = ny ? 1.5707963267948966 : 3.141592653589793;          // pi/2, pi
-      const double lo = ny ? 6.123233995736766e-17 : 1.2246467991473532e-16;  // their low parts
-      r = copysign(hi, y) + (ny ? copysign(lo, y) - t : copysign(lo, y) + t);
-    }
-  }
-  if (RAZOR) {
-    const double deg = SF_DIV(fabs(r), M_PI) * 180, kd = rint(deg);
-    const bool rz = !(ny | nx) & (fabs(deg - kd) < 1e-9) & (y != 0.0);
-    if (__ballot(rz) != 0ull) {
-      if (rz) {
-        const double* e = kDegDD[(int)kd];  // (phi_hi, phi_lo, cos_hi, cos_lo, sin_hi, sin_lo) of kd degrees
-        const double ph = e[0], pl = e[1], ch = e[2], cl = e[3], sh = e[4], sl = e[5];
-        const double p1 = ay * ch, e1 = __builtin_fma(ay, ch, -p1);
-        const double p2 = x * sh, e2 = __builtin_fma(x, sh, -p2);
-        const double d = p1 - p2;  // nearly cancels
-        const double bb = d - p1, err = (p1 - (d - bb)) + (-p2 - bb);  // two-sum error term of p1 + (-p2)
-        const double lo = err + (e1 - e2) + (ay * cl - x * sl);
-        const double N = d + lo, D = x * ch + ay * sh;
-        r = copysign(ph + (pl + N / D), y);
-      }
-    }
-  }
-  return r;
-}
 
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants): counter
 // (c0, c1, 0, 0), key (k0, k1); the first output word.  The reference's rollout gets its actions from the policy
@@ -328,182 +137,12 @@ __device__ __forceinline__ void score(float amount, float& rew, Lane& L) {
   if (L.points < 0) L.points = 0;
 }
 
-// Hexagon::isInside (SRC/hexagon.cpp:36-48).  The edges (nx, ny, px, py) are compile-time
-// constants (sf_layout.h: both radii are the same in every preset), so they are immediates.
-// For the two horizontal edges of each hexagon nx is -0.0, so  nx*dx + ny*dy < 0  is exactly
-// ny*dy < 0 (adding a zero changes nothing, a zero product is not < 0), i.e. a plain comparison
-// of y against the edge: y < py for ny > 0, y > py for ny < 0 (the sign of a difference of two
-// doubles is exact, and scaling by |ny| >= 1 cannot flush it to zero).  Eight multiplies, eight
-// subtractions and four additions less per ship and tick, same truth value for every finite y.
-// The six truth values are folded arithmetically: "no edge value is < 0" is "the smallest edge value is not < 0"
-// (for the horizontal edges the value is the difference y - py or py - y; -0.0 is not < 0 either way; no NaN
-// here), one comparison per hexagon instead of six whose results meet in scalar registers.
-#define SF_EDGE_TEST(nx, ny, px, py)                                                                  \
-  m = __builtin_fmin(m, (nx) == 0.0 ? ((ny) > 0 ? y - (py) : (py) - y) : (nx) * (x - (px)) + (ny) * (y - (py)));
-__device__ __forceinline__ bool inside_big_hex(double x, double y) {
-  double m = 1.0;
-  SF_BIG_HEX_EDGES(SF_EDGE_TEST)
-  return !(m < 0);
-}
-__device__ __forceinline__ bool inside_small_hex(double x, double y) {
-  double m = 1.0;
-  SF_SMALL_HEX_EDGES(SF_EDGE_TEST)
-  return !(m < 0);
-}
-#undef SF_EDGE_TEST
-#define SF_EDGE_TEST(nx, ny, px, py)                                     \
-  if ((nx) == 0.0)                                                       \
-    in = in & !((ny) > 0 ? (y < (py)) : (y > (py)));                     \
-  else                                                                   \
-    in = in & !((nx) * (x - (px)) + (ny) * (y - (py)) < 0);
-#undef SF_EDGE_TEST
-
-// Game::isOutsideGameArea (SRC/game.cpp:129-131)
-__device__ __forceinline__ bool outside_area(const SfKernelArgs& a, double x, double y) {
-  return (x < 0) | (x > sfc::width_d) | (y > sfc::height_d) | (y < 0);
-}
-
-// Game::resetShip (SRC/game.cpp:133-149).  The accepted (x, y, angle) of the rejection loop over
-// libc rand() is a fixed sequence per seed: the host precomputed it (sf_spawn_table) and each
-// lane walks it with its own cursor.
-// `e` = the lane's next table entry, packed (x, y, angle, 0) as four int16
-__device__ __forceinline__ void spawn_ship_from(const SfKernelArgs& a, Lane& L, unsigned long long e) {
-  L.cursor += 1;
-  L.sx = (double)(int16_t)(e & 0xFFFFu);
-  L.sy = (double)(int16_t)((e >> 16) & 0xFFFFu);
-  L.angle = (int16_t)((e >> 32) & 0xFFFFu);
-  L.vx = a.start_vx;
-  L.vy = a.start_vy;
-  L.fl |= SF_FL_SHIP_ALIVE;
-}
-__device__ __forceinline__ void spawn_ship(const SfKernelArgs& a, Lane& L) {
-  spawn_ship_from(a, L, *reinterpret_cast<const unsigned long long*>(a.spawn + 4 * (size_t)(L.cursor & a.spawn_mask)));
-}
-
-// Game::Game (SRC/game.cpp:18-82); statistics and episode sums are zeroed by the caller
-__device__ __forceinline__ void new_game(const SfKernelArgs& a, Lane& L) {
-  L.fl = 0;
-  spawn_ship(a, L);
-  L.fl |= SF_FL_FORT_ALIVE;
-  L.fort_angle = 180;  // :40
-  L.fort_last = 0;     // :41
-  L.points = 0;
-  L.raw = 0;
-  L.vlner = 0;
-  L.time = 0;
-  L.death_t = L.fire_t = L.thrust_t = L.left_t = L.right_t = 0;
-  L.fort_t = L.fort_death_t = 0;
-  L.fort_vuln_t = sfc::vuln_time;  // :78 adds to a never-initialised member; defined as 0 + 250
-  L.mmask = L.smask = 0;
-  L.kc0 = L.kc1 = 0;  // statistics start over with the game (SRC/game.cpp:18-82)
-  L.ep_return = 0;
-  L.c_resets = L.c_missed = L.c_incs = L.c_maxv = L.c_big = L.c_small = L.c_shell = L.c_destroyed = 0;
-  L.ep_kills = 0;
-  // (L.mpool belongs to the tile, not to the game: the caller maintains it)
-}
-
 __device__ __forceinline__ void kill_ship(Lane& L, StatDelta& S) {  // SRC/game.cpp:274-280
   if (L.fl & SF_FL_SHIP_ALIVE) {
     L.fl &= ~SF_FL_SHIP_ALIVE;
     L.death_t = 0;
     S.ship_deaths += 1;
   }
-}
-
-// The fixed part of a lane: eight 16-byte chunks (sf_layout.h), in two sets.  The start of a launch is a chip-wide burst --
-// every wave of every CU pulls its state at once and the fabric delivers about 12 bytes per cycle and CU -- so what the
-// first phases of the tick need (keys, respawn, ship, fortress: flags and angles, masks, the timers, position and
-// velocity) is issued FIRST and waited for alone; the two chunks that are first read at the shells or later (score,
-// counts) and the missile pool rows are issued behind the dependent loads of round trip 2 and arrive under the
-// key / ship / fortress arithmetic.
-struct LaneLate {
-  i4_t ta, sc;
-};
-__device__ __forceinline__ void load_lane_early(const unsigned char* tb, const Off& o, Lane& L) {
-  const i4_t mi = SF_LD(i4_t, SF_CHUNK(misc, 0), o.o16);  // first: the projectile prefetch waits on the masks
-  const i4_t sm = SF_LD(i4_t, SF_CHUNK(small, 0), o.o16);
-  const d2_t p = SF_LD(d2_t, SF_CHUNK(ship_pos, 0), o.o16);
-  const d2_t v = SF_LD(d2_t, SF_CHUNK(ship_vel, 0), o.o16);
-  const i4_t tc = SF_LD(i4_t, SF_CHUNK(timers_b, 0), o.o16);
-  L.right_t = (int)(int16_t)(tc.x & 0xFFFF);
-  L.ep_return = (int)((unsigned)tc.x & 0xFFFF0000u);  // bits 16..31; the low half comes with the late set
-  L.fort_t = tc.y;
-  L.fort_death_t = tc.z;
-  L.fort_vuln_t = tc.w;
-  L.death_t = mi.x;
-  L.cursor = (unsigned)mi.y & 0xFFFFFFu;
-  L.c_destroyed = (unsigned)mi.y >> 24;
-  L.mmask = (unsigned)mi.z & SF_MASK_LOW;
-  L.mpool = (unsigned)mi.z >> SF_MPOOL_SHIFT;
-  L.smask = (unsigned)mi.w & SF_MASK_LOW;
-  L.ep_kills = (unsigned)mi.w >> SF_KILLS_SHIFT;
-  L.sx = p.x;
-  L.sy = p.y;
-  L.vx = v.x;
-  L.vy = v.y;
-  L.angle = (int16_t)(sm.x & 0xFFFF);
-  L.fort_angle = (int16_t)((unsigned)sm.x >> 16);
-  L.fort_last = (int16_t)(sm.y & 0xFFFF);
-  L.fl = ((unsigned)sm.y >> 16) & 0xFFu;
-  L.kc0 = (unsigned)sm.z;
-  L.kc1 = (unsigned)sm.w;
-}
-__device__ __forceinline__ LaneLate load_lane_late(const unsigned char* tb, const Off& o) {
-  LaneLate t;
-  t.ta = SF_LD(i4_t, SF_CHUNK(timers_a, 0), o.o16);
-  t.sc = SF_LD(i4_t, SF_CHUNK(score, 0), o.o16);
-  return t;
-}
-__device__ __forceinline__ void unpack_lane_late(const LaneLate& t, Lane& L) {
-  const unsigned w_pvl = (unsigned)t.ta.x, w_fire = (unsigned)t.ta.y, w_thr = (unsigned)t.ta.z, w_left = (unsigned)t.ta.w;
-  const unsigned w_vl = (unsigned)t.sc.z, w_time = (unsigned)t.sc.w;
-  L.prev_vlner = (int)(w_pvl & 0xFFFu);
-  L.c_incs = (w_pvl >> 12) & 0xFFFu;
-  L.c_big = w_pvl >> 24;
-  L.fire_t = (int)(int16_t)(w_fire & 0xFFFFu);
-  L.c_resets = w_fire >> 16;
-  L.thrust_t = (int)(int16_t)(w_thr & 0xFFFFu);
-  L.c_missed = w_thr >> 16;
-  L.left_t = (int)(int16_t)(w_left & 0xFFFFu);
-  L.ep_return = (int)((unsigned)L.ep_return | (w_left >> 16));  // the high half came with timers_b
-  L.points = __int_as_float(t.sc.x);
-  L.raw = __int_as_float(t.sc.y);
-  L.vlner = (int)(w_vl & 0xFFFu);
-  L.c_maxv = (w_vl >> 12) & 0xFFFu;
-  L.c_small = w_vl >> 24;
-  L.time = (int)(w_time & 0xFFFFFFu);
-  L.c_shell = w_time >> 24;
-}
-
-// The lane's seven chunks back to the tile, through the wave's descriptor: the chunk offsets ride in the scalar
-// offset, no 64-bit address per store; write-through (SF_SC_AUX).
-__device__ __forceinline__ void store_lane_buf(__amdgpu_buffer_rsrc_t rs, const Off& o, const Lane& L) {
-  constexpr int aux = SF_SC_AUX;
-#define SF_BST16(group, v) \
-  sf_buf_st128<aux>(__builtin_bit_cast(u4_t, v), rs, o.o16, SF_GOFF(group, 0))
-  SF_BST16(ship_pos, (d2_t{L.sx, L.sy}));
-  SF_BST16(ship_vel, (d2_t{L.vx, L.vy}));
-  // the packed words of sf_layout.h (SF_W_*): a value below, a per-episode counter above
-  const unsigned er = (unsigned)L.ep_return;
-  SF_BST16(timers_a, (i4_t{(int)(((unsigned)L.prev_vlner & 0xFFFu) | ((L.c_incs & 0xFFFu) << 12) | (L.c_big << 24)),
-                           (int)(((unsigned)L.fire_t & 0xFFFFu) | (L.c_resets << 16)),
-                           (int)(((unsigned)L.thrust_t & 0xFFFFu) | (L.c_missed << 16)),
-                           (int)(((unsigned)L.left_t & 0xFFFFu) | (er << 16))}));
-  SF_BST16(timers_b, (i4_t{(int)(((unsigned)L.right_t & 0xFFFFu) | (er & 0xFFFF0000u)), L.fort_t, L.fort_death_t, L.fort_vuln_t}));
-  SF_BST16(score, (i4_t{__float_as_int(L.points), __float_as_int(L.raw),
-                        (int)(((unsigned)L.vlner & 0xFFFu) | ((L.c_maxv & 0xFFFu) << 12) | (L.c_small << 24)),
-                        (int)(((unsigned)L.time & 0xFFFFFFu) | (L.c_shell << 24))}));
-  SF_BST16(misc, (i4_t{L.death_t, (int)((L.cursor & 0xFFFFFFu) | (L.c_destroyed << 24)), (int)(L.mmask | (L.mpool << SF_MPOOL_SHIFT)),
-                       (int)(L.smask | (L.ep_kills << SF_KILLS_SHIFT))}));
-#undef SF_BST16
-  sf_buf_st128<aux>(
-      u4_t{(unsigned)(L.angle & 0xFFFF) | ((unsigned)(L.fort_angle & 0xFFFF) << 16),
-           (unsigned)(L.fort_last & 0xFFFF) | ((L.fl & 0xFFFFu) << 16), L.kc0, L.kc1},
-      rs, o.o16, SF_GOFF(small, 0));
-}
-
-__device__ __forceinline__ void store_lane(unsigned char* tb, const Off& o, const Lane& L) {
-  store_lane_buf(__builtin_amdgcn_make_buffer_rsrc(tb, 0, (int)sfl::kTileBytes, 0x00020000), o, L);
 }
 
 // Agent-scope (L2-coherent, L1-bypassing) accesses for the few places where one launch may read
@@ -525,121 +164,6 @@ __device__ __forceinline__ d2_t ld_coherent_d2(const unsigned char* p) {
 }
 __device__ __forceinline__ void st_coherent_i32(unsigned char* p, int v) {
   __hip_atomic_store(reinterpret_cast<int*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ExtraGameValues of Game::computeExtra (SRC/game.cpp:282-312).  They are a pure function of the
-// ship state (frozen while the ship is dead), so they are derived for the observation instead of
-// being stored.  a_pos = atan2(sy - fy, sx - fx) is shared with updateFortress, a_vel =
-// atan2(vy, vx); both are evaluated side by side so the two dependency chains interleave.
-struct Extras {
-  double aim, vdir, ndist;
-};
-
-__device__ __forceinline__ Extras compute_extras(const SfKernelArgs& a, const Lane& L, double a_pos, double a_vel) {
-  Extras e;
-  // aim (SRC/game.cpp:299-305)
-  double o = rad2deg(a_pos) - (double)L.angle + 180;
-  if (o < -180) o = o + 360;
-  e.aim = o;
-  // vdir (SRC/game.cpp:286-297).  norm()==0 iff vx*vx+vy*vy==0.  The reference's first atan2 is
-  // atan2(-(fy-sy), fx-sx) = atan2(dy, -dx) = +-pi - a_pos: derived from a_pos (observation-only
-  // value, differs from a second libm call by <= 1 ulp of pi).
-  {
-    const double dy = L.sy - sfc::fort_y;
-    double ov;
-    if (dy == 0)  // on the fortress row the two calls sit on different branch cuts: call it
-      ov = sf_atan2<false>(-(sfc::fort_y - L.sy), sfc::fort_x - L.sx);
-    else
-      ov = dy < 0 ? (-M_PI - a_pos) : (M_PI - a_pos);
-    double diff = a_vel - ov;
-    if (diff > M_PI) diff -= M_PI * 2;
-    if (diff < -M_PI) diff += M_PI * 2;
-    e.vdir = (L.vx * L.vx + L.vy * L.vy == 0.0) ? 0.0 : rad2deg(diff);
-  }
-  // fdist, ndist (SRC/game.cpp:310-311): the y term of the reference subtracts the ship from
-  // itself, so fdist = sqrt(dx^2 + 0) = |dx|.
-  const double fdist = fabs(L.sx - sfc::fort_x);
-  e.ndist = -1 + SF_DIV(fdist - sfc::ndist_a, sfc::ndist_b);
-  return e;
-}
-
-// One observation row (ENV:95-157) written to `o` (an LDS staging row or global memory).
-template <typename T>
-__device__ __forceinline__ void write_obs(const SfKernelArgs& a, T* o, const Lane& L, const Extras& e) {
-  const int n_missiles = __popc(L.mmask);
-  const int n_shells = a.real_shell_count ? __popc(L.smask) : n_missiles;  // SRC/pymodule.cpp:131-134
-  // ENV:148 reads the vulnerability timer through a getter with undefined behaviour
-  // (SRC/pymodule.cpp:44-45); the intended predicate is used.
-  const int kill_ready = (L.vlner > 10 && L.fort_vuln_t < sfc::vuln_time) ? 1 : 0;
-  const int n_keys_t = a.obs_dim - 15;
-  const int timers[4] = {L.fire_t, L.thrust_t, L.left_t, L.right_t};  // SRC/pymodule.cpp:98-105
-  const bool ship_alive = L.fl & SF_FL_SHIP_ALIVE, fort_alive = L.fl & SF_FL_FORT_ALIVE;
-  if (a.obs_type == 2) {  // monitors, ENV:96-108
-    o[0] = (T)(n_missiles > 0 ? 0.5 : -0.5);
-    o[1] = (T)(fort_alive ? 0.5 : -0.5);
-    o[2] = (T)(L.vlner > 10 ? 0.5 : -0.5);
-    o[3] = (T)(kill_ready ? 0.5 : -0.5);
-    o[4] = (T)(e.aim < 3 ? 0.5 : -0.5);
-    o[5] = (T)(e.aim > 3 ? 0.5 : -0.5);
-    o[6] = (T)(e.ndist > .75 ? 0.5 : -0.5);
-    o[7] = (T)(e.ndist > .25 ? 0.5 : -0.5);
-    o[8] = (T)(e.ndist < -.25 ? 0.5 : -0.5);
-    o[9] = (T)(e.ndist < -.75 ? 0.5 : -0.5);
-  } else if (a.obs_type == 1) {  // normalized-features, ENV:109-133
-    double f[19];
-    f[0] = ship_alive ? 1 : 0;
-    f[1] = SF_DIV(L.sx, sfc::pb_width);
-    f[2] = SF_DIV(L.sy, sfc::pb_height);
-    f[3] = SF_DIV(L.vx, 10);
-    f[4] = SF_DIV(L.vy, 10);
-    f[5] = SF_DIV((double)L.angle, 360);
-    f[6] = SF_DIV(e.aim, 180);
-    {
-      double m = fmod(e.vdir, 360.0);  // Python float %: result takes the divisor's sign
-      if (m != 0) {
-        if (m < 0) m += 360.0;
-      } else {
-        m = 0.0;
-      }
-      f[7] = SF_DIV(m, 360);
-    }
-    f[8] = e.ndist;
-    f[9] = fort_alive ? 1 : 0;
-    f[10] = SF_DIV((double)L.fort_angle, 360);
-    f[11] = SF_DIV((double)(L.vlner > 10 ? L.vlner : 10), 10);  // ENV:122 max(), as written
-    f[12] = kill_ready;
-    f[13] = SF_DIV((double)n_missiles, SF_MAX_MISSILES_D);
-    f[14] = SF_DIV((double)n_shells, SF_MAX_MISSILES_D);
-#pragma unroll
-    for (int k = 0; k < 4; k++) f[15 + k] = SF_DIV((double)timers[k], sfc::max_ticks);
-#pragma unroll
-    for (int k = 0; k < 19; k++) {
-      if (k < 15 + n_keys_t) {
-        double v = f[k];
-        v = v < -1 ? -1 : (v > 1 ? 1 : v);
-        o[k] = (T)v;
-      }
-    }
-  } else {  // features, ENV:134-157
-    o[0] = (T)(ship_alive ? 1 : 0);
-    o[1] = (T)L.sx;
-    o[2] = (T)L.sy;
-    o[3] = (T)L.vx;
-    o[4] = (T)L.vy;
-    o[5] = (T)L.angle;
-    o[6] = (T)e.aim;
-    o[7] = (T)e.vdir;
-    o[8] = (T)e.ndist;
-    o[9] = (T)(fort_alive ? 1 : 0);
-    o[10] = (T)L.fort_angle;
-    o[11] = (T)L.vlner;
-    o[12] = (T)kill_ready;
-    o[13] = (T)n_missiles;
-    o[14] = (T)n_shells;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (k < n_keys_t) o[15 + k] = (T)timers[k];
-  }
 }
 
 // The default observation -- obs_type 'features', float32, full waves, 16-byte aligned output -- with everything
@@ -789,89 +313,12 @@ __global__ __launch_bounds__(SF_BLOCK) void sf_reset_kernel(SfKernelArgs a, int 
   L.mpool = 0;  // every env of the tile starts over: the tile's missile pool is empty
   store_lane(tb, o, L);
   if (obs != nullptr && i < (unsigned)a.n_envs && a.obs_type != 3) {
-    // the reference's extras are stale heap until the first tick; defined as computeExtra(spawn) -- or, by flag, as the zeros
-    // a fresh process's heap holds there (SF_FLAG_REF_RESET_OBS)
+    // new_game_extras (sf_lane_dev.h), spelled out: inlined as a function, this kernel's selects come out in another order
+    // (profiles/state_ops_split.md).  A one-line clean-up for the change that next alters this kernel on purpose.
     Extras e = compute_extras(a, L, sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x), sf_atan2<false>(L.vy, L.vx));
     if (a.ref_reset_obs) e = Extras{0.0, 0.0, 0.0};
-    if (a.obs_f64)
-      write_obs<double>(a, (double*)obs + (size_t)i * a.obs_dim, L, e);
-    else
-      write_obs<float>(a, (float*)obs + (size_t)i * a.obs_dim, L, e);
+    write_obs_row(a, obs, i, L, e);
   }
-}
-
-// ---------------------------------------------------------------------------------------------
-// sf_reset_lanes: env.reset() in the envs the caller marks (ENV:163-178), the others play on.  One wave per tile, a lane
-// per env; mask = uint8 [n_envs], any non-zero byte marks its env (no byte at or beyond n_envs is read).  A tile without a
-// marked env returns before it writes anything.  Otherwise the marked lanes start a new game exactly as sf_reset_kernel's
-// re-reset does -- prev_vlner and the spawn cursor are the lane's own --, and their missiles leave the tile's pool: the
-// kept lanes' entries go through LDS by (owner, slot) and the pool is rebuilt slot by slot with ballot + prefix count,
-// the order sf_slots_to_mpool_kernel and sf_lanes_load_kernel give; the new count goes into every lane's missile word.
-// A kept lane's chunks, shells and slots are as before (only WHERE its entries sit in the pool may differ, which no row
-// and no tick can tell); the lanes behind the batch in a partial last tile count as kept.  obs (may be null): the marked
-// lanes' rows as sf_reset_kernel writes them; no other row is touched.  hint (image batches): the marked lanes' bits are
-// cleared -- a new game's ship did not die in the last tick.
-__global__ __launch_bounds__(64) void sf_reset_lanes_kernel(SfKernelArgs a, const uint8_t* mask, void* obs) {
-  __shared__ d2_t spos[64][SF_NSLOT];
-  __shared__ unsigned short sang[64][SF_NSLOT];
-  const unsigned lane = threadIdx.x;
-  const long tile_i = blockIdx.x;
-  const long e = tile_i * 64 + lane;
-  const bool marked = e < a.n_envs && mask[e] != 0;
-  const unsigned long long rmask = __ballot(marked);
-  if (rmask == 0ull) return;  // (uniform)
-  unsigned char* const tb = a.state + (size_t)tile_i * sfl::kTileBytes;
-  const Off o = {lane * 16u, lane * 8u, lane * 4u, lane * 2u, lane};
-  // everything that is read from the tile, first
-  const i4_t mi = SF_LD(i4_t, SF_CHUNK(misc, 0), o.o16);
-  const unsigned pvl_w = SF_LD(unsigned, SF_CHUNK(timers_a, 0), o.o16);
-  const unsigned n_pool = (unsigned)__builtin_amdgcn_readfirstlane(mi.z) >> SF_MPOOL_SHIFT;  // (the same in every lane of the tile)
-  for (unsigned i = lane; i < n_pool && i < 64u * SF_NSLOT; i += 64) {  // (the pool holds 64 * SF_NSLOT entries)
-    const unsigned m = SF_LD(unsigned, SF_CHUNK(missile_meta, 0), i * 4u);
-    const unsigned ow = SF_MM_OWNER(m);
-    if (!((rmask >> ow) & 1ull) && SF_MM_SLOT(m) < (unsigned)SF_NSLOT) {  // (a slot tag is below SF_NSLOT; the LDS rows hold no more)
-      spos[ow][SF_MM_SLOT(m)] = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), i * 16u);
-      sang[ow][SF_MM_SLOT(m)] = (unsigned short)SF_MM_ANGLE(m);
-    }
-  }
-  const unsigned kept = marked ? 0u : ((unsigned)mi.z & SF_MASK_LOW);
-  __syncthreads();
-  // the pool, slot by slot (sf_slots_to_mpool_kernel's order)
-  unsigned wp = 0;
-  for (int s = 0; s < SF_NSLOT; s++) {
-    const bool live = (kept >> s) & 1u;
-    const unsigned long long b = __ballot(live);
-    const unsigned idx = wp + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-    wp += (unsigned)__popcll(b);
-    if (live) {
-      *reinterpret_cast<d2_t*>(SF_CHUNK(missile_pos, 0) + (size_t)idx * 16) = spos[lane][s];
-      *reinterpret_cast<unsigned*>(SF_CHUNK(missile_meta, 0) + (size_t)idx * 4) = SF_MM_PACK(sang[lane][s] & 511u, lane, s);
-    }
-  }
-  if (!marked) {
-    *reinterpret_cast<unsigned*>(SF_CHUNK(misc, 0) + o.o16 + 8u) = kept | (wp << SF_MPOOL_SHIFT);
-  } else {
-    Lane L;
-    L.prev_vlner = (int)(pvl_w & 0xFFFu);
-    L.cursor = (unsigned)mi.y;
-    new_game(a, L);
-    L.mpool = wp;
-    store_lane(tb, o, L);
-    if (obs != nullptr && a.obs_type != 3) {  // (sf_reset_kernel's observation of a new game)
-      Extras x = compute_extras(a, L, sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x), sf_atan2<false>(L.vy, L.vx));
-      if (a.ref_reset_obs) x = Extras{0.0, 0.0, 0.0};
-      if (a.obs_f64)
-        write_obs<double>(a, (double*)obs + (size_t)e * a.obs_dim, L, x);
-      else
-        write_obs<float>(a, (float*)obs + (size_t)e * a.obs_dim, L, x);
-    }
-  }
-  if (a.hint && lane == 0) a.hint[tile_i] &= ~rmask;
-}
-
-hipError_t sf_launch_reset_lanes(const SfKernelArgs& a, const uint8_t* mask, void* obs, hipStream_t stream) {
-  hipLaunchKernelGGL(sf_reset_lanes_kernel, dim3((unsigned)((a.n_envs + 63) / 64)), dim3(64), 0, stream, a, mask, obs);
-  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1831,306 +1278,6 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
 }
 
 // ---------------------------------------------------------------------------------------------
-// The envs' draw records (sf_drawrec.h) from the state as it is in HBM: what the image instantiations of the step kernel
-// leave behind themselves, for a state that got there any other way -- a reset, sf_set_field, a batch that steps with a
-// symbolic observation and renders now and then.  One wave per tile, a lane per env; the pool's entries file their
-// transforms at [owner][slot] and tell their owners through LDS where they come near the score / the bar, exactly like the
-// step kernel's m_row.  Same functions, same values: tests/test_gpu_image.py compares the two byte for byte.
-__global__ __launch_bounds__(64) void sf_drawrec_kernel(const unsigned char* state, const double* consts, int n_envs,
-                                                       unsigned char* draw, int pics) {
-  __shared__ unsigned near[64];
-  typedef float f4_t __attribute__((ext_vector_type(4)));
-  const unsigned lane = threadIdx.x;
-  const long tile_i = blockIdx.x;
-  const unsigned char* tb = state + tile_i * sfl::kTileBytes;
-  unsigned char* const dr = draw + tile_i * (long)SF_DR_TILE_BYTES;
-  const unsigned o16 = lane * 16u;
-  const d2_t sp = SF_LD(d2_t, SF_CHUNK(ship_pos, 0), o16);
-  const i4_t tc = SF_LD(i4_t, SF_CHUNK(timers_b, 0), o16);
-  const i4_t sc = SF_LD(i4_t, SF_CHUNK(score, 0), o16);
-  const i4_t mi = SF_LD(i4_t, SF_CHUNK(misc, 0), o16);
-  const i4_t sm = SF_LD(i4_t, SF_CHUNK(small, 0), o16);
-  near[lane] = 0u;
-  __syncthreads();
-  const unsigned n_pool = (unsigned)__builtin_amdgcn_readfirstlane(mi.z) >> SF_MPOOL_SHIFT;  // (the same in every lane of the tile)
-  for (unsigned k = lane; k < n_pool; k += 64) {
-    const d2_t p = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), k * 16u);
-    const unsigned m = SF_LD(unsigned, SF_CHUNK(missile_meta, 0), k * 4u);
-    *reinterpret_cast<d2_t*>(dr + (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_MISSILE0 + SF_MM_SLOT(m)) * SF_DR_PIECE_STRIDE + SF_MM_OWNER(m) * SF_DR_LANE_STRIDE) = p;
-    *reinterpret_cast<int16_t*>(dr + SF_DR_ANGLES_OFF + 2 * SF_MM_SLOT(m) + SF_MM_OWNER(m) * SF_DR_LANE_STRIDE) = (int16_t)SF_MM_ANGLE(m);
-    const unsigned f = sfd::hud_flags_near((float)p.x, (float)p.y, sfd::kMissileExt);
-    if (f) atomicOr(&near[SF_MM_OWNER(m)], f);
-  }
-  const unsigned smask = (unsigned)mi.w & SF_MASK_LOW, mmask = (unsigned)mi.z & SF_MASK_LOW;
-  unsigned proj = 0u;
-  for (unsigned rest = smask; rest; rest &= rest - 1u) {
-    const int s = __ffs(rest) - 1;
-    const d2_t q = SF_LD(d2_t, SF_CHUNK(shell_pos, s), o16);
-    proj |= sfd::hud_flags_near((float)q.x, (float)q.y, sfd::kShellExt);
-  }
-  __syncthreads();
-  proj |= near[lane];
-  if (tile_i * 64 + lane >= n_envs) return;
-  const int ship_angle = (int16_t)(sm.x & 0xFFFF), fort_angle = (int16_t)((unsigned)sm.x >> 16);
-  const unsigned fl = ((unsigned)sm.y >> 16) & 0xFFu;
-  const sfd::Header h = sfd::make_header(sp.x, sp.y, ship_angle, (fl & SF_FL_SHIP_ALIVE) != 0u, (fl & SF_FL_FORT_ALIVE) != 0u, fort_angle,
-                                         __int_as_float(sc.x), sc.z & 0xFFF, tc.w, mmask, smask, proj, pics != 0,
-                                         (int)((unsigned)sc.w & 0xFFFFFFu));
-  unsigned char* const me = dr + lane * SF_DR_LANE_STRIDE;
-  *reinterpret_cast<u4_t*>(me) = u4_t{h.w[0], h.w[1], h.w[2], h.w[3]};
-  *reinterpret_cast<u4_t*>(me + SF_DR_PIECE_STRIDE) = u4_t{h.w[4], h.w[5], h.w[6], h.w[7]};
-  *reinterpret_cast<d2_t*>(me + (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_SHIP) * SF_DR_PIECE_STRIDE) = sp;
-  (void)consts;
-}
-
-hipError_t sf_launch_drawrec(const SfKernelArgs& a, hipStream_t stream) {
-  if (!a.draw) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_drawrec_kernel, dim3((unsigned)(a.lanes / 64)), dim3(64), 0, stream, a.state, a.consts, a.n_envs, a.draw,
-                     a.draw_pics);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// sf_get_field / sf_set_field: one field between the tiled state and a linear [count][n_envs]
-// buffer (not on the hot path).
-template <typename T>
-__global__ __launch_bounds__(SF_BLOCK) void sf_field_copy_kernel(unsigned char* state, int n_envs, long tile_off,
-                                                                int lane_stride, int slot_stride, int count,
-                                                                T* linear, int to_linear) {
-  const long e = (long)blockIdx.x * SF_BLOCK + threadIdx.x;
-  if (e >= n_envs) return;
-  unsigned char* lane0 = state + (e >> 6) * sfl::kTileBytes + tile_off + (e & 63) * lane_stride;
-  for (int c = 0; c < count; c++) {
-    T* p = reinterpret_cast<T*>(lane0 + (long)c * slot_stride);
-    if (to_linear)
-      linear[(long)c * n_envs + e] = *p;
-    else
-      *p = linear[(long)c * n_envs + e];
-  }
-}
-
-// sf_get_field / sf_set_field for the fields that are not one element at a fixed place of a chunk (sf_layout.h: SF_FK_*).
-
-// "stats": the reference's 13 ints (SRC/game.hh:29-43) from / to their bit fields (sf_layout.h: SF_W_*); ship deaths
-// (row 3) is the sum of rows 0-2 and is not stored (a value written to it is ignored).
-__global__ __launch_bounds__(SF_BLOCK) void sf_stats_copy_kernel(unsigned char* state, int n_envs, int32_t* linear,
-                                                                int to_linear) {
-  const long e = (long)blockIdx.x * SF_BLOCK + threadIdx.x;
-  if (e >= n_envs) return;
-  unsigned char* tile = state + (e >> 6) * sfl::kTileBytes;
-  const long lo = (e & 63) * 16;
-  uint16_t* kc = reinterpret_cast<uint16_t*>(tile + sfl::chunk_offset(SF_G_small, 0) + lo + SF_KEYCOUNT_BYTE);
-  uint32_t* ta = reinterpret_cast<uint32_t*>(tile + sfl::chunk_offset(SF_G_timers_a, 0) + lo);  // pvl, fire, thrust, left
-  uint32_t* sc = reinterpret_cast<uint32_t*>(tile + sfl::chunk_offset(SF_G_score, 0) + lo);     // .., .., vlner, time
-  uint32_t* mi = reinterpret_cast<uint32_t*>(tile + sfl::chunk_offset(SF_G_misc, 0) + lo);      // .., cursor, .., ..
-#define SF_ROW(k) linear[(long)(k) * n_envs + e]
-#define SF_PUT(word, shift, bits, k) word = (word & ~((((1u << (bits)) - 1u)) << (shift))) | (((uint32_t)SF_ROW(k) & ((1u << (bits)) - 1u)) << (shift))
-  if (to_linear) {
-    const int big = (int)(ta[0] >> 24), sml = (int)(sc[2] >> 24), shl = (int)(sc[3] >> 24);
-    SF_ROW(SF_ST_BIG_HEX_DEATHS) = big;
-    SF_ROW(SF_ST_SMALL_HEX_DEATHS) = sml;
-    SF_ROW(SF_ST_SHELL_DEATHS) = shl;
-    SF_ROW(SF_ST_SHIP_DEATHS) = big + sml + shl;
-    SF_ROW(SF_ST_RESETS) = (int)(ta[1] >> 16);
-    SF_ROW(SF_ST_DESTROYED) = (int)(mi[1] >> 24);
-    SF_ROW(SF_ST_MISSED) = (int)(ta[2] >> 16);
-    for (int c = 0; c < SF_ST_KEY_COUNT; c++) SF_ROW(SF_ST_KEY_FIRST + c) = kc[c];
-    SF_ROW(SF_ST_VLNER_INCS) = (int)((ta[0] >> 12) & 0xFFFu);
-    SF_ROW(SF_ST_MAX_VLNER) = (int)((sc[2] >> 12) & 0xFFFu);
-  } else {
-    SF_PUT(ta[0], 24, 8, SF_ST_BIG_HEX_DEATHS);
-    SF_PUT(sc[2], 24, 8, SF_ST_SMALL_HEX_DEATHS);
-    SF_PUT(sc[3], 24, 8, SF_ST_SHELL_DEATHS);
-    SF_PUT(ta[1], 16, 16, SF_ST_RESETS);
-    SF_PUT(mi[1], 24, 8, SF_ST_DESTROYED);
-    SF_PUT(ta[2], 16, 16, SF_ST_MISSED);
-    for (int c = 0; c < SF_ST_KEY_COUNT; c++) kc[c] = (uint16_t)SF_ROW(SF_ST_KEY_FIRST + c);
-    SF_PUT(ta[0], 12, 12, SF_ST_VLNER_INCS);
-    SF_PUT(sc[2], 12, 12, SF_ST_MAX_VLNER);
-  }
-#undef SF_PUT
-#undef SF_ROW
-}
-
-// a bit field of a 32-bit word of the lane's chunk (sf_layout.h: SF_BITFIELDS) from / to a linear int32 buffer
-__global__ __launch_bounds__(SF_BLOCK) void sf_bits_copy_kernel(unsigned char* state, int n_envs, long tile_off, int shift,
-                                                               int bits, int is_signed, uint32_t* linear, int to_linear) {
-  const long e = (long)blockIdx.x * SF_BLOCK + threadIdx.x;
-  if (e >= n_envs) return;
-  uint32_t* w = reinterpret_cast<uint32_t*>(state + (e >> 6) * sfl::kTileBytes + tile_off + (e & 63) * 16);
-  const uint32_t mask = bits >= 32 ? ~0u : ((1u << bits) - 1u);
-  if (to_linear) {
-    uint32_t v = (*w >> shift) & mask;
-    if (is_signed && bits < 32 && (v >> (bits - 1))) v |= ~mask;
-    linear[e] = v;
-  } else {
-    *w = (*w & ~(mask << shift)) | ((linear[e] & mask) << shift);
-  }
-}
-// "ep_return": int32, bits 0..15 above the left timer, bits 16..31 above the right timer
-__global__ __launch_bounds__(SF_BLOCK) void sf_epret_copy_kernel(unsigned char* state, int n_envs, int32_t* linear, int to_linear) {
-  const long e = (long)blockIdx.x * SF_BLOCK + threadIdx.x;
-  if (e >= n_envs) return;
-  unsigned char* tile = state + (e >> 6) * sfl::kTileBytes;
-  uint32_t* wl = reinterpret_cast<uint32_t*>(tile + sfl::chunk_offset(SF_G_timers_a, 0) + (e & 63) * 16 + 12);
-  uint32_t* wr = reinterpret_cast<uint32_t*>(tile + sfl::chunk_offset(SF_G_timers_b, 0) + (e & 63) * 16);
-  if (to_linear) {
-    linear[e] = (int32_t)((*wl >> 16) | (*wr & 0xFFFF0000u));
-  } else {
-    const uint32_t v = (uint32_t)linear[e];
-    *wl = (*wl & 0xFFFFu) | (v << 16);
-    *wr = (*wr & 0xFFFFu) | (v & 0xFFFF0000u);
-  }
-}
-
-// The missile fields, per env and slot as the reference has them (mMissiles[i], SRC/game.hh:90), from / to the tile's pool.
-// `slots` is the batch's slot-major view [SF_NSLOT][n_envs] of (x, y) as d2_t and of the heading as int32.
-// Pool -> slots: every live entry goes to (slot, owner); slots without a missile read 0.
-__global__ __launch_bounds__(64) void sf_mpool_to_slots_kernel(const unsigned char* state, int n_envs, d2_t* sl_pos,
-                                                              int32_t* sl_ang) {
-  const long tile_i = blockIdx.x;
-  const unsigned lane = threadIdx.x;
-  const unsigned char* tile = state + tile_i * sfl::kTileBytes;
-  const long e = tile_i * 64 + lane;
-  if (e < n_envs)
-    for (int s = 0; s < SF_NSLOT; s++) {
-      sl_pos[(long)s * n_envs + e] = d2_t{0, 0};
-      sl_ang[(long)s * n_envs + e] = 0;
-    }
-  __syncthreads();
-  const unsigned n = *reinterpret_cast<const uint32_t*>(tile + sfl::chunk_offset(SF_G_misc, 0) + 8) >> SF_MPOOL_SHIFT;
-  for (unsigned k = lane; k < n; k += 64) {
-    const d2_t p = *reinterpret_cast<const d2_t*>(tile + sfl::chunk_offset(SF_G_missile_pos, 0) + (size_t)k * 16);
-    const unsigned m = *reinterpret_cast<const uint32_t*>(tile + sfl::chunk_offset(SF_G_missile_meta, 0) + (size_t)k * 4);
-    const long oe = tile_i * 64 + SF_MM_OWNER(m);
-    if (oe < n_envs) {
-      sl_pos[(long)SF_MM_SLOT(m) * n_envs + oe] = p;
-      sl_ang[(long)SF_MM_SLOT(m) * n_envs + oe] = (int)SF_MM_ANGLE(m);
-    }
-  }
-}
-// Slots -> pool: the tile's pool is rebuilt from the alive masks, slot by slot (ballot + prefix count, the step
-// kernel's compaction), and the count written into every lane's missile word.
-__global__ __launch_bounds__(64) void sf_slots_to_mpool_kernel(unsigned char* state, int n_envs, const d2_t* sl_pos,
-                                                              const int32_t* sl_ang) {
-  const long tile_i = blockIdx.x;
-  const unsigned lane = threadIdx.x;
-  unsigned char* tile = state + tile_i * sfl::kTileBytes;
-  const long e = tile_i * 64 + lane;
-  uint32_t* mw = reinterpret_cast<uint32_t*>(tile + sfl::chunk_offset(SF_G_misc, 0) + lane * 16 + 8);
-  const unsigned mask = e < n_envs ? (*mw & SF_MASK_LOW) : 0u;
-  unsigned wp = 0;
-  for (int s = 0; s < SF_NSLOT; s++) {
-    const bool live = (mask >> s) & 1u;
-    const unsigned long long b = __ballot(live);
-    const unsigned idx = wp + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-    wp += (unsigned)__popcll(b);
-    if (live) {
-      *reinterpret_cast<d2_t*>(tile + sfl::chunk_offset(SF_G_missile_pos, 0) + (size_t)idx * 16) = sl_pos[(long)s * n_envs + e];
-      *reinterpret_cast<uint32_t*>(tile + sfl::chunk_offset(SF_G_missile_meta, 0) + (size_t)idx * 4) =
-          SF_MM_PACK((unsigned)sl_ang[(long)s * n_envs + e] & 511u, lane, s);
-    }
-  }
-  *mw = mask | (wp << SF_MPOOL_SHIFT);
-}
-
-hipError_t sf_launch_mpool_to_slots(const unsigned char* state, int n_envs, void* sl_pos, int32_t* sl_ang, hipStream_t stream) {
-  hipLaunchKernelGGL(sf_mpool_to_slots_kernel, dim3((unsigned)((n_envs + 63) / 64)), dim3(64), 0, stream, state, n_envs,
-                     (d2_t*)sl_pos, sl_ang);
-  return hipGetLastError();
-}
-hipError_t sf_launch_slots_to_mpool(unsigned char* state, long lanes, int n_envs, const void* sl_pos, const int32_t* sl_ang,
-                                    hipStream_t stream) {
-  hipLaunchKernelGGL(sf_slots_to_mpool_kernel, dim3((unsigned)(lanes / 64)), dim3(64), 0, stream, state, n_envs,
-                     (const d2_t*)sl_pos, sl_ang);
-  return hipGetLastError();
-}
-
-// one component of the slot-major missile view <-> the caller's linear [SF_NSLOT][n_envs] buffer
-// which: 0 = x, 1 = y (double), 2 = heading (int16)
-__global__ __launch_bounds__(SF_BLOCK) void sf_mslot_component_kernel(d2_t* sl_pos, int32_t* sl_ang, long total, int which,
-                                                                     void* linear, int to_linear) {
-  const long k = (long)blockIdx.x * SF_BLOCK + threadIdx.x;
-  if (k >= total) return;
-  if (which == 2) {
-    if (to_linear) ((int16_t*)linear)[k] = (int16_t)sl_ang[k];
-    else sl_ang[k] = ((const int16_t*)linear)[k];
-  } else {
-    double* comp = reinterpret_cast<double*>(sl_pos + k) + which;
-    if (to_linear) ((double*)linear)[k] = *comp;
-    else *comp = ((const double*)linear)[k];
-  }
-}
-hipError_t sf_launch_mslot_component(void* sl_pos, int32_t* sl_ang, long total, int which, void* linear, int to_linear,
-                                     hipStream_t stream) {
-  hipLaunchKernelGGL(sf_mslot_component_kernel, dim3((unsigned)((total + SF_BLOCK - 1) / SF_BLOCK)), dim3(SF_BLOCK), 0, stream,
-                     (d2_t*)sl_pos, sl_ang, total, which, linear, to_linear);
-  return hipGetLastError();
-}
-
-// PMC calibration (sf_calibration_copy): copy whole 16-byte chunks of one group to the linear
-// buffer -- 16 B per lane, 1 KiB per wave-instruction, exactly the step kernel's access pattern.
-__global__ __launch_bounds__(SF_BLOCK) void sf_group_copy_kernel(const unsigned char* state, int n_envs, long tile_off,
-                                                                int slots, i4_t* linear) {
-  const long e = (long)blockIdx.x * SF_BLOCK + threadIdx.x;
-  if (e >= n_envs) return;
-  const unsigned char* lane0 = state + (e >> 6) * sfl::kTileBytes + tile_off + (e & 63) * 16;
-  for (int c = 0; c < slots; c++)
-    linear[(long)c * n_envs + e] = *reinterpret_cast<const i4_t*>(lane0 + (long)c * 16 * sfl::kTileLanes);
-}
-
-hipError_t sf_launch_group_copy(const unsigned char* state, int n_envs, int group, unsigned char* linear,
-                                hipStream_t stream) {
-  const unsigned grid = (unsigned)((n_envs + SF_BLOCK - 1) / SF_BLOCK);
-  hipLaunchKernelGGL(sf_group_copy_kernel, dim3(grid), dim3(SF_BLOCK), 0, stream, state, n_envs,
-                     sfl::group_offset(group), sfl::kGroups[group].slots, (i4_t*)linear);
-  return hipGetLastError();
-}
-
-hipError_t sf_launch_field_copy(unsigned char* state, int n_envs, int field, unsigned char* linear, int to_linear,
-                                hipStream_t stream) {
-  const sfl::FieldMeta& m = sfl::kFields[field];
-  const unsigned grid = (unsigned)((n_envs + SF_BLOCK - 1) / SF_BLOCK);
-  if (m.kind == SF_FK_STATS) {
-    hipLaunchKernelGGL(sf_stats_copy_kernel, dim3(grid), dim3(SF_BLOCK), 0, stream, state, n_envs, (int32_t*)linear, to_linear);
-    return hipGetLastError();
-  }
-  if (m.kind == SF_FK_BITS) {
-    const sfl::BitField bf = sfl::bit_field(field);
-    hipLaunchKernelGGL(sf_bits_copy_kernel, dim3(grid), dim3(SF_BLOCK), 0, stream, state, n_envs,
-                       sfl::group_offset(m.group) + m.byte_in_chunk, bf.shift, bf.bits, bf.is_signed, (uint32_t*)linear, to_linear);
-    return hipGetLastError();
-  }
-  if (m.kind == SF_FK_EPRET) {
-    hipLaunchKernelGGL(sf_epret_copy_kernel, dim3(grid), dim3(SF_BLOCK), 0, stream, state, n_envs, (int32_t*)linear, to_linear);
-    return hipGetLastError();
-  }
-  if (m.kind == SF_FK_MPOOL) return hipErrorInvalidValue;  // sf_capi.cpp goes through the slot view (sf_launch_mslot_component)
-  const int lane_stride = sfl::kGroups[m.group].chunk, slot_stride = lane_stride * sfl::kTileLanes;
-  const long off = sfl::group_offset(m.group) + m.byte_in_chunk;
-  const int elem_size = m.elem_size, count = m.count;
-  switch (elem_size) {
-    case 1:
-      hipLaunchKernelGGL(sf_field_copy_kernel<uint8_t>, dim3(grid), dim3(SF_BLOCK), 0, stream, state, n_envs, off,
-                         lane_stride, slot_stride, count, (uint8_t*)linear, to_linear);
-      break;
-    case 2:
-      hipLaunchKernelGGL(sf_field_copy_kernel<uint16_t>, dim3(grid), dim3(SF_BLOCK), 0, stream, state, n_envs, off,
-                         lane_stride, slot_stride, count, (uint16_t*)linear, to_linear);
-      break;
-    case 4:
-      hipLaunchKernelGGL(sf_field_copy_kernel<uint32_t>, dim3(grid), dim3(SF_BLOCK), 0, stream, state, n_envs, off,
-                         lane_stride, slot_stride, count, (uint32_t*)linear, to_linear);
-      break;
-    default:
-      hipLaunchKernelGGL(sf_field_copy_kernel<uint64_t>, dim3(grid), dim3(SF_BLOCK), 0, stream, state, n_envs, off,
-                         lane_stride, slot_stride, count, (uint64_t*)linear, to_linear);
-      break;
-  }
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
 // launchers (called by sf_capi.cpp)
 
 hipError_t sf_launch_reset(const SfKernelArgs& a, int first, unsigned cursor0, unsigned stride, void* obs,
@@ -2206,240 +1353,5 @@ hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, con
 #undef SF_GO1
 #undef SF_GO_SPLIT
 #undef SF_GO2
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Lane states (sfmi.h: sf_save_lanes / sf_load_lanes / sf_copy_lanes): one env's whole game state as a row of
-// SF_LANE_STATE_BYTES, independent of the lane and the tile it came from.  A row is 71 pieces of 16 bytes:
-//   0        header (SF_LANE_STATE_MAGIC | version, preset, seed, spawn table length) -- sfmi.h
-//   1 .. 7   the lane's chunks of ship_pos, ship_vel, timers_a, timers_b, score, misc, small (the tile's pool count that rides
-//            above the missile mask is cleared: it belongs to the tile)
-//   8 .. 47  its shell_pos / shell_vel chunks, slots 0 .. 19 each
-//   48 .. 67 its missiles by SLOT, (x, y) -- out of the tile's pool by owner and slot as sf_mpool_to_slots_kernel takes them;
-//            a slot without a missile is zero
-//   68 .. 70 their headings as uint16, slots 0 .. 19, then zeros
-// Save: one wave per row; the row's 71 pieces leave as one 1136-byte run of consecutive 16-byte stores.  Load: one wave
-// per destination tile the call touches, which rebuilds the tile's pool from the lanes it keeps and the rows it takes.
-static_assert(SF_LANE_STATE_BYTES == 16 * 71, "sfmi.h: the row's pieces");
-constexpr int kLsPieces = 71, kLsBase = 1, kLsShell = 8, kLsMis = 48, kLsAng = 68;
-static_assert(SF_G_ship_pos == 0 && SF_G_small == 6 && sfl::chunk_offset(SF_G_small) == 6 * 1024 &&
-                  sfl::chunk_offset(SF_G_shell_vel) == sfl::chunk_offset(SF_G_shell_pos, SF_NSLOT),
-              "the row copies the seven one-slot groups, then the shell groups, as runs of 1 KiB rows");
-
-__device__ __forceinline__ long sf_lane_index(const void* idx, int idx64, long k) {
-  return idx64 ? (long)reinterpret_cast<const long long*>(idx)[k] : (long)reinterpret_cast<const int*>(idx)[k];
-}
-
-// piece p (1 .. 47) of lane l: its byte offset inside the tile
-__device__ __forceinline__ unsigned sf_ls_chunk_off(int p, unsigned l) {
-  return (p < kLsShell ? (unsigned)(p - kLsBase) * 1024u : (unsigned)sfl::chunk_offset(SF_G_shell_pos) + (unsigned)(p - kLsShell) * 1024u) +
-         16u * l;
-}
-
-__global__ __launch_bounds__(64) void sf_lanes_save_kernel(const unsigned char* state, int n_envs, const void* lanes, int idx64,
-                                                          unsigned char* rows, u4_t header, unsigned long long* refused) {
-  __shared__ d2_t mpos[SF_NSLOT];
-  __shared__ unsigned mang[SF_NSLOT];
-  const long k = blockIdx.x;
-  const unsigned lane = threadIdx.x;
-  const long e = lanes ? sf_lane_index(lanes, idx64, k) : k;
-  unsigned char* const row = rows + k * (long)SF_LANE_STATE_BYTES;
-  if (e < 0 || e >= n_envs) {  // (uniform) no such lane: a row no batch takes
-    if (lane == 0) {
-      *reinterpret_cast<u4_t*>(row) = u4_t{0u, 0u, 0u, 0u};
-      atomicAdd(refused, 1ull);
-    }
-    return;
-  }
-  const unsigned char* const tb = state + (e >> 6) * sfl::kTileBytes;
-  const unsigned l = (unsigned)(e & 63);
-  if (lane < SF_NSLOT) {
-    mpos[lane] = d2_t{0.0, 0.0};
-    mang[lane] = 0u;
-  }
-  __syncthreads();
-  const unsigned n_pool = SF_LD(unsigned, SF_CHUNK(misc, 0), 16u * l + 8u) >> SF_MPOOL_SHIFT;
-  for (unsigned i = lane; i < n_pool; i += 64) {
-    const unsigned m = SF_LD(unsigned, SF_CHUNK(missile_meta, 0), i * 4u);
-    if (SF_MM_OWNER(m) == l) {
-      mpos[SF_MM_SLOT(m)] = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), i * 16u);
-      mang[SF_MM_SLOT(m)] = SF_MM_ANGLE(m);
-    }
-  }
-  __syncthreads();
-  for (int p = (int)lane; p < kLsPieces; p += 64) {
-    u4_t v;
-    if (p == 0) {
-      v = header;
-    } else if (p < kLsMis) {
-      v = SF_LD(u4_t, tb, sf_ls_chunk_off(p, l));
-      if (p == kLsBase + SF_G_misc) v.z &= SF_MASK_LOW;  // (the tile's pool count: not the lane's)
-    } else if (p < kLsAng) {
-      v = __builtin_bit_cast(u4_t, mpos[p - kLsMis]);
-    } else {
-      unsigned w[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int s = 8 * (p - kLsAng) + 2 * j;
-        w[j] = (s < SF_NSLOT ? mang[s] : 0u) | ((s + 1 < SF_NSLOT ? mang[s + 1] : 0u) << 16);
-      }
-      v = u4_t{w[0], w[1], w[2], w[3]};
-    }
-    *reinterpret_cast<u4_t*>(row + 16 * p) = v;
-  }
-}
-
-// Load, pass 1: every (lane, row) pair of the call is checked -- lane inside the batch, row index inside the rows, the row's
-// header the batch's -- and counted where it is not; the accepted ones file k into map[lane] with atomicMax (the LAST
-// occurrence of a lane wins) and their tile into the list of tiles pass 2 visits (once each: the tile's flag).
-__global__ __launch_bounds__(SF_BLOCK) void sf_lanes_mark_kernel(int n_envs, const void* lanes, int idx64, int n,
-                                                                const unsigned char* rows, const void* row_idx, long n_rows, u4_t header,
-                                                                int* map, unsigned* tflag, unsigned* tlist, unsigned* tcount,
-                                                                unsigned long long* refused) {
-  const long k = (long)blockIdx.x * SF_BLOCK + threadIdx.x;
-  if (k >= n) return;
-  const long e = lanes ? sf_lane_index(lanes, idx64, k) : k;
-  const long r = row_idx ? sf_lane_index(row_idx, idx64, k) : k;
-  bool ok = e >= 0 && e < n_envs && r >= 0 && r < n_rows;
-  if (ok) {
-    const u4_t h = *reinterpret_cast<const u4_t*>(rows + r * (long)SF_LANE_STATE_BYTES);
-    ok = h.x == header.x && h.y == header.y && h.z == header.z && h.w == header.w;
-  }
-  if (!ok) {
-    atomicAdd(refused, 1ull);
-    return;
-  }
-  atomicMax(&map[e], (int)k);
-  if (atomicExch(&tflag[e >> 6], 1u) == 0u) tlist[atomicAdd(tcount, 1u)] = (unsigned)(e >> 6);
-}
-
-// Load, pass 2: one wave per listed tile (a grid-stride loop over the list).  The lanes that take a row get its chunks; the
-// tile's missile pool is rebuilt from the kept lanes' entries and the rows' slots, slot by slot with ballot + prefix count --
-// the order sf_slots_to_mpool_kernel gives -- and its count goes into every lane's missile word.  map / flags are left as
-// pass 1 found them (-1 / 0) for the next call.  obs (may be null): the restored lanes' observation rows, computed from the
-// restored state by the step kernel's functions (compute_extras with the bearings as the step computes them, write_obs).
-__global__ __launch_bounds__(64) void sf_lanes_load_kernel(SfKernelArgs a, const unsigned char* rows, const void* row_idx, int idx64,
-                                                          int* map, unsigned* tflag, const unsigned* tlist, const unsigned* tcount,
-                                                          void* obs) {
-  __shared__ d2_t spos[64][SF_NSLOT];
-  __shared__ unsigned short sang[64][SF_NSLOT];
-  __shared__ __attribute__((aligned(16))) unsigned char stage[7 * 1024];  // restored lanes' seven chunks, tile layout (obs)
-  const unsigned lane = threadIdx.x;
-  const unsigned n_tiles = *tcount;
-  for (unsigned ti = blockIdx.x; ti < n_tiles; ti += gridDim.x) {
-    const unsigned t = tlist[ti];
-    unsigned char* const tb = a.state + (size_t)t * sfl::kTileBytes;
-    const long e = (long)t * 64 + lane;
-    const int k = map[e];
-    const bool restored = k >= 0;
-    const unsigned char* const row =
-        restored ? rows + (row_idx ? sf_lane_index(row_idx, idx64, k) : (long)k) * (long)SF_LANE_STATE_BYTES : nullptr;
-    const unsigned long long rmask = __ballot(restored);
-    // everything that is read from the tile, first
-    const unsigned kept_mw = SF_LD(unsigned, SF_CHUNK(misc, 0), 16u * lane + 8u);
-    const unsigned n_pool = (unsigned)__builtin_amdgcn_readfirstlane(kept_mw) >> SF_MPOOL_SHIFT;
-    for (unsigned i = lane; i < n_pool; i += 64) {
-      const unsigned m = SF_LD(unsigned, SF_CHUNK(missile_meta, 0), i * 4u);
-      const unsigned o = SF_MM_OWNER(m);
-      if (!((rmask >> o) & 1ull)) {
-        spos[o][SF_MM_SLOT(m)] = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), i * 16u);
-        sang[o][SF_MM_SLOT(m)] = (unsigned short)SF_MM_ANGLE(m);
-      }
-    }
-    unsigned mask = e < a.n_envs ? (kept_mw & SF_MASK_LOW) : 0u;
-    if (restored) {
-#pragma unroll 4
-      for (int s = 0; s < SF_NSLOT; s++) spos[lane][s] = SF_LD(d2_t, row, 16 * (kLsMis + s));
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const u4_t w = SF_LD(u4_t, row, 16 * (kLsAng + j));
-        const unsigned ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int q = 0; q < 8; q++)
-          if (8 * j + q < SF_NSLOT) sang[lane][8 * j + q] = (unsigned short)(ww[q >> 1] >> (16 * (q & 1)));
-      }
-      mask = SF_LD(unsigned, row, 16 * (kLsBase + SF_G_misc) + 8) & SF_MASK_LOW;
-    }
-    __syncthreads();
-    // the pool, slot by slot (sf_slots_to_mpool_kernel's order)
-    unsigned wp = 0;
-    for (int s = 0; s < SF_NSLOT; s++) {
-      const bool live = (mask >> s) & 1u;
-      const unsigned long long b = __ballot(live);
-      const unsigned idx = wp + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-      wp += (unsigned)__popcll(b);
-      if (live) {
-        *reinterpret_cast<d2_t*>(SF_CHUNK(missile_pos, 0) + (size_t)idx * 16) = spos[lane][s];
-        *reinterpret_cast<unsigned*>(SF_CHUNK(missile_meta, 0) + (size_t)idx * 4) = SF_MM_PACK(sang[lane][s] & 511u, lane, s);
-      }
-    }
-    if (restored) {
-      // eight pieces in flight at a time: (the row and the tile might alias as far as the compiler knows -- one piece per
-      // round trip otherwise)
-      for (int p0 = kLsBase; p0 < kLsMis; p0 += 8) {
-        u4_t v[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = p0 + j < kLsMis ? SF_LD(u4_t, row, 16 * (p0 + j)) : u4_t{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const int p = p0 + j;
-          if (p >= kLsMis) break;
-          if (p == kLsBase + SF_G_misc) v[j].z = mask | (wp << SF_MPOOL_SHIFT);
-          if (p < kLsShell) *reinterpret_cast<u4_t*>(stage + (p - kLsBase) * 1024 + 16 * lane) = v[j];
-          *reinterpret_cast<u4_t*>(tb + sf_ls_chunk_off(p, lane)) = v[j];
-        }
-      }
-    } else {
-      *reinterpret_cast<unsigned*>(SF_CHUNK(misc, 0) + 16u * lane + 8u) = mask | (wp << SF_MPOOL_SHIFT);
-      for (int g = 0; g < 7; g++) *reinterpret_cast<u4_t*>(stage + g * 1024 + 16 * lane) = u4_t{0u, 0u, 0u, 0u};  // (defined values below)
-    }
-    map[e] = -1;
-    if (lane == 0) tflag[t] = 0u;
-    if (obs != nullptr && a.obs_type != 3 && rmask != 0ull) {  // (uniform)
-      Lane L;
-      const Off o = {lane * 16u, lane * 8u, lane * 4u, lane * 2u, lane};
-      load_lane_early(stage, o, L);
-      unpack_lane_late(load_lane_late(stage, o), L);
-      // the bearings as the tick that made this state computed them: a new game's (time 0: sf_reset, an auto-reset) with the
-      // reset's atan2, any other with the step's table form; SF_FLAG_REF_RESET_OBS zeroes a new game's extras
-      const bool fresh = L.time == 0;
-      const double* atab = a.consts + SF_CONST_ATAB;
-      const double a_pos = fresh ? sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x)
-                                 : sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x, atab);
-      const double a_vel = fresh ? sf_atan2<false>(L.vy, L.vx) : sf_atan2_core(L.vy, L.vx, atab);
-      Extras x = compute_extras(a, L, a_pos, a_vel);
-      if (fresh && a.ref_reset_obs) x = Extras{0.0, 0.0, 0.0};
-      if (restored) {
-        if (a.obs_f64)
-          write_obs<double>(a, (double*)obs + (size_t)e * a.obs_dim, L, x);
-        else
-          write_obs<float>(a, (float*)obs + (size_t)e * a.obs_dim, L, x);
-      }
-    }
-    __syncthreads();  // (the LDS rows are the next tile's)
-  }
-}
-
-hipError_t sf_launch_lanes_save(const unsigned char* state, int n_envs, const void* lanes, int idx64, int n, unsigned char* rows,
-                                const uint32_t header[4], unsigned long long* refused, hipStream_t stream) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(sf_lanes_save_kernel, dim3((unsigned)n), dim3(64), 0, stream, state, n_envs, lanes, idx64, rows,
-                     u4_t{header[0], header[1], header[2], header[3]}, refused);
-  return hipGetLastError();
-}
-
-hipError_t sf_launch_lanes_load(const SfKernelArgs& a, const void* lanes, int idx64, int n, const unsigned char* rows, const void* row_idx,
-                                long n_rows, const uint32_t header[4], int* map, unsigned* tflag, unsigned* tlist, unsigned* tcount,
-                                unsigned long long* refused, void* obs, hipStream_t stream) {
-  if (n <= 0) return hipSuccess;
-  hipError_t e = hipMemsetAsync(tcount, 0, sizeof(unsigned), stream);
-  if (e != hipSuccess) return e;
-  const u4_t h{header[0], header[1], header[2], header[3]};
-  hipLaunchKernelGGL(sf_lanes_mark_kernel, dim3((unsigned)((n + SF_BLOCK - 1) / SF_BLOCK)), dim3(SF_BLOCK), 0, stream, a.n_envs, lanes,
-                     idx64, n, rows, row_idx, n_rows, h, map, tflag, tlist, tcount, refused);
-  const long tiles = a.lanes / 64;
-  const unsigned grid = (unsigned)(n < tiles ? n : tiles);
-  hipLaunchKernelGGL(sf_lanes_load_kernel, dim3(grid), dim3(64), 0, stream, a, rows, row_idx, idx64, map, tflag, tlist, tcount, obs);
   return hipGetLastError();
 }

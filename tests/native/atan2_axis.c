@@ -1,4 +1,4 @@
-/* Host check of the near-axis form of atan2 the step kernel uses (sf_kernels.hip: sf_atan2): next to the y axis
+/* Host check of the near-axis form of atan2 the step kernel uses (sf_lane_dev.h: sf_atan2): next to the y axis
  * +-pi/2 - x/y, next to the negative x axis +-pi + y/x, pi in two doubles, one rounding -- must be glibc's atan2 bit
  * for bit (the reference engine is glibc's; the device libm differs from it in the last bit now and then, and on
  * these two axes that bit decides the fortress sector).  usage: atan2_axis [samples]; exit status 1 on a mismatch. */

@@ -1,4 +1,4 @@
-/* Host restatement of sf_atan2_core (sf_kernels.hip): the table-step atan2 of the step kernel's hot path.  Same
+/* Host restatement of sf_atan2_core (sf_lane_dev.h): the table-step atan2 of the step kernel's hot path.  Same
  * operations in the same order (FMAs where the kernel has them); the hardware's v_rcp_f64 seed is modelled as the
  * reciprocal rounded to FLOAT -- a worse seed than the instruction's -- so that the two Newton steps are what carries
  * the precision.  Reports the largest distance from the host libm's atan2 in ulps over random arguments and over

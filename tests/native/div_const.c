@@ -1,4 +1,4 @@
-/* Host check of the three-operation constant division the step kernel uses (sf_kernels.hip: sf_div_const):
+/* Host check of the three-operation constant division the step kernel uses (sf_lane_dev.h: sf_div_const):
  * for every divisor on the kernel's path, q' = fma(fma(-c, RN(a*rc), a), rc, RN(a*rc)) with rc = RN(1/c) must be
  * the IEEE quotient a / c, bit for bit.  Operands: the value ranges the kernel feeds it, and random significands over
  * 120 binades.  Prints the number of mismatches per divisor; exit status 1 if any.  usage: div_const [samples] */

@@ -50,3 +50,18 @@ def aimed_hunter_actions(env, T, rng):
         if done:
             obs = env.reset()
     return acts
+
+
+def firing_actions(T, n, n_actions, seed):
+    """Seeded random actions, FIRE (action 1 of every action set, ENV:211-229) half of the time: many missiles in flight."""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, n_actions, (T, n))
+    return np.where(rng.random((T, n)) < 0.5, 1, a).astype(np.uint8)
+
+
+def largest_pool(env):
+    """The most entries any tile's missile pool holds, from the envs' alive masks."""
+    mm = env.get_field("missile_mask").astype(np.uint32)
+    per_env = np.array([bin(int(m)).count("1") for m in mm])
+    pad = np.zeros((-len(per_env)) % 64, per_env.dtype)
+    return int(np.concatenate([per_env, pad]).reshape(-1, 64).sum(1).max())

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from sfcompare import compare_state, obs_close
-from sfscript import open_loop_actions
+from sfscript import firing_actions, largest_pool, open_loop_actions
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -331,3 +331,40 @@ def test_graph_capture_of_load_and_step(sfa):
     G.check_lanes()
     sg, se = G.state_dict(), E.state_dict()
     assert not [k for k in sg if not _same_bits(sg[k], se[k])]
+
+
+def test_every_pool_rebuild_plays_the_same_games(sfa):
+    """A tile's missile pool is rebuilt in three places (sf_state_ops.hip: pool_rebuild): by a lane-state load, by the slot view
+    behind load_state_dict and by the masked reset.  Batch A plays until its pools span more than one row; B takes A's lane
+    states, C its state_dict; all three get the same masked reset (marks in the first tile and in the partial last one, where
+    the lanes behind the batch count as kept and have no missiles) and then play the same 60 random actions: every output
+    equal bit for bit at every tick, state_dict() equal field by field at the end.  160 envs: two full tiles and one of 32."""
+    n = 160
+    A, B, C = (sfa.SFVecEnv(n, gametype="youturn", action_set=1, spawn_stride=1) for _ in range(3))
+    A.rollout(torch.from_numpy(firing_actions(400, n, A.n_actions, seed=11)).to(A.device), want_obs=False)
+    pool = largest_pool(A)
+    assert pool > 64, "the largest pool holds %d entries: one row" % pool
+    mask = np.zeros(n, np.uint8)
+    mask[0:64:2] = 1      # the first tile: every other lane
+    mask[128:160:3] = 1   # the partial tile
+    owns = A.get_field("missile_mask") != 0
+    mixed = [t for t in range(3) if (owns & (mask != 0))[64 * t:64 * t + 64].any() and (owns & (mask == 0))[64 * t:64 * t + 64].any()]
+    print("largest pool %d entries; tiles where a marked and a kept lane own missiles: %s" % (pool, mixed))
+    assert mixed, "no tile in which a marked lane and a kept lane both own a missile"
+    B.load_lanes(A.save_lanes())
+    C.load_state_dict(A.state_dict())
+    md = torch.from_numpy(mask).to(A.device)
+    sel = md != 0
+    oa, ob, oc = (E.reset_lanes(mask=md) for E in (A, B, C))
+    assert torch.equal(_bits(oa)[sel], _bits(ob)[sel]) and torch.equal(_bits(oa)[sel], _bits(oc)[sel])
+    acts = torch.from_numpy(np.random.default_rng(12).integers(0, A.n_actions, (60, n)).astype(np.uint8)).to(A.device)
+    for t in range(60):
+        ra, rb, rc = (E.step_tensors(acts[t]) for E in (A, B, C))
+        for name, x, y, z in zip(("obs", "reward", "done", "info"), ra, rb, rc):
+            assert torch.equal(_bits(x), _bits(y)), (t, name, "lane states")
+            assert torch.equal(_bits(x), _bits(z)), (t, name, "state_dict")
+    sa, sb, sc = A.state_dict(), B.state_dict(), C.state_dict()
+    assert not [k for k in sa if not _same_bits(sa[k], sb[k])]
+    assert not [k for k in sa if not _same_bits(sa[k], sc[k])]
+    for E in (A, B, C):
+        E.close()

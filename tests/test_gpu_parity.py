@@ -546,7 +546,7 @@ def test_autoturn_heading_on_the_spawn_lattice(sfa, oracle_mod):
 def test_bearings_a_whisker_off_the_axes(sfa, oracle_mod, gametype):
     """Ships a few ulps to 1e-9 off the fortress column / row: the bearing is a hair off +-90 or +-180 degrees --
     sector boundaries -- and the side the ROUNDED atan2 falls on decides the fortress sector (and the autoturn
-    heading).  The device forms atan2 there as glibc rounds it (sf_kernels.hip: sf_atan2); a soak once found sector
+    heading).  The device forms atan2 there as glibc rounds it (sf_lane_dev.h: sf_atan2); a soak once found sector
     280 against the reference's 270 for a ship at x = 355 + 2^-44."""
     O = oracle_mod
     rng = np.random.default_rng(5)
@@ -848,7 +848,7 @@ def test_full_size_hunter_sample(sfa, oracle_mod, gametype):
 def test_batches_beyond_one_wave_per_simd(sfa, oracle_mod, gametype, obs_type):
     """Up to 65 536 envs a wave is alone on its SIMD; beyond, several share one, and the hardware's timing differs: a 128-bit
     buffer store whose data register the next instruction overwrites lost lanes 12-15 of every 16 there (found in round 4:
-    the compiler covers that hazard only for stores with an immediate soffset; sf_buf_st128 in sf_kernels.hip).  262 144
+    the compiler covers that hazard only for stores with an immediate soffset; sf_buf_st128 in sf_lane_dev.h).  262 144
     envs in ONE batch must play exactly the games of the same envs in four batches of 65 536 -- every field of the state,
     bit for bit -- and 96 lanes of the big batch, the hazard's lanes among them, the oracle's games."""
     O = oracle_mod

@@ -12,6 +12,7 @@ import pytest
 
 from eplogref import EpisodeLogModel
 from sfcompare import compare_state, obs_close
+from sfscript import firing_actions as _actions, largest_pool as _largest_pool
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -35,26 +36,11 @@ def _make(sfa, n, gametype="youturn", **kw):
     return sfa.SFVecEnv(n, gametype=gametype, action_set=1, spawn_stride=1, **kw)
 
 
-def _actions(T, n, n_actions, seed):
-    """Seeded random actions, FIRE (action 1 of every action set, ENV:211-229) half of the time: many missiles in flight."""
-    rng = np.random.default_rng(seed)
-    a = rng.integers(0, n_actions, (T, n))
-    return np.where(rng.random((T, n)) < 0.5, 1, a).astype(np.uint8)
-
-
 def _warm(envs, T, seed):
     e0 = envs[0]
     a = torch.from_numpy(_actions(T, e0.num_envs, e0.n_actions, seed)).to(e0.device)
     for e in envs:
         e.rollout(a, want_obs=False)
-
-
-def _largest_pool(env):
-    """The most entries any tile's missile pool holds, from the envs' alive masks."""
-    mm = env.get_field("missile_mask").astype(np.uint32)
-    per_env = np.array([bin(int(m)).count("1") for m in mm])
-    pad = np.zeros((-len(per_env)) % 64, per_env.dtype)
-    return int(np.concatenate([per_env, pad]).reshape(-1, 64).sum(1).max())
 
 
 def _worth_resetting(env):

@@ -1,6 +1,6 @@
 /* How often can the device's autoturn heading differ from the reference's?  (tools/, diagnostic; not on the product path.)
  *
- * sf_atan2 (sf_kernels.hip) is correctly rounded within 1e-9 degrees of an integer degree; glibc 2.35's atan2 is not
+ * sf_atan2 (sf_lane_dev.h) is correctly rounded within 1e-9 degrees of an integer degree; glibc 2.35's atan2 is not
  * always (0.50x-ulp errors), so on such an argument the two can differ in the last bit, and when the bit decides
  * ceil(bearing in degrees) the autoturn heading (SRC/game.cpp:318-319) -- or the fortress sector (:205) -- differs by one
  * step.  This program PLAYS the game (the plain-C restatement of the engine, oracle/sf_oracle.c, which calls the
