@@ -348,6 +348,8 @@ int sf_check_actions(sf_batch* b, void* stream);
  * sf_set_field of one field repairs that field and leaves the count alone (other fields, other envs may have wrapped).
  * Auto-resetting batches start every field over at each episode end and cannot get there.  sf_set_field refuses
  * (SF_ERR_ARG) values that do not fit a field, and a `stats` row 3 (ship deaths) that is not the sum of rows 0-2.
+ * A `missile_angle` (int16 here, nine bits in the tile's missile pool) outside 0 .. 511 is refused the same way, with a text
+ * that names env and slot, before anything is copied.
  * The hand-over counter of split launches (an internal error, never seen) is reported the same way and by sf_episode_stats
  * (which then still delivers the statistics and clears nothing); it is cleared by nothing: make a new batch. */
 int sf_check_state(sf_batch* b, void* stream);

@@ -1180,6 +1180,21 @@ static int field_copy(sf_batch* b, int f, void* host, size_t bytes, bool to_host
         }
     }
   }
+  if (!to_host && f == SF_F_missile_angle) {
+    // int16 on this side, 9 bits in a pool entry (sf_layout.h: SF_MM_*): the same rule -- pool_rebuild would keep the low
+    // nine bits, and -1 would fly as heading 511, past the 360 entries of the trig table
+    const int16_t* v = (const int16_t*)host;
+    const long n = b->n_envs;
+    const int max_heading = (int)SF_MM_ANGLE(~0u);
+    for (int s = 0; s < SF_NSLOT; s++)
+      for (long e = 0; e < n; e++) {
+        const int x = v[(long)s * n + e];
+        if (x < 0 || x > max_heading) {
+          sf_set_error("sf_set_field(missile_angle): heading %d of env %ld, slot %d does not fit a pool entry's 9 bits", x, e, s);
+          return SF_ERR_ARG;
+        }
+      }
+  }
   DeviceGuard guard(b->device);
   HIP_TRY(hipDeviceSynchronize());
   const bool mview = m.kind == SF_FK_MPOOL;                      // missile_x / missile_y / missile_angle

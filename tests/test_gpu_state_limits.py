@@ -133,6 +133,18 @@ def test_set_field_refuses_what_a_field_cannot_hold(sfa):
         with pytest.raises(ValueError):
             env.set_field(name, v)
         env.set_field(name, sd[name])  # what fits is accepted
+    # a missile's heading: int16 on this side, nine bits in the tile's pool -- -1 once flew as heading 511
+    ang = sd["missile_angle"].copy()
+    for bad in (-1, 512):
+        v = ang.copy()
+        v[19, 3] = bad
+        with pytest.raises(ValueError, match="env 3, slot 19"):
+            env.set_field("missile_angle", v)
+        assert np.array_equal(env.get_field("missile_angle"), ang)  # refused before anything is copied
+    for good in (511, 0):
+        v = ang.copy()
+        v[19, 3] = good
+        env.set_field("missile_angle", v)
     env.set_field("vlner", np.full(8, 4095, np.int32))
     env.set_field("fire_timer", np.full(8, -32768, np.int32))
     st = sd["stats"].copy()
