@@ -477,8 +477,8 @@ extern "C" int sf_create(const sf_create_params* p, sf_batch** out) {
     HIP_TRY_FREE(hipMemset(a.hint, 0, (size_t)(lanes / 64) * sizeof(unsigned long long)));
   }
 #ifdef SF_STAMPS  // diagnostic build (tools/stamps.py): per-wave clock stamps, never in the product
-  HIP_TRY_FREE(hipMalloc((void**)&a.dbg, (size_t)(lanes / 64) * 16 * sizeof(unsigned long long)));
-  HIP_TRY_FREE(hipMemset(a.dbg, 0, (size_t)(lanes / 64) * 16 * sizeof(unsigned long long)));
+  HIP_TRY_FREE(hipMalloc((void**)&a.dbg, (size_t)(lanes / 64) * SF_STAMP_SLOTS * sizeof(unsigned long long)));
+  HIP_TRY_FREE(hipMemset(a.dbg, 0, (size_t)(lanes / 64) * SF_STAMP_SLOTS * sizeof(unsigned long long)));
 #endif
 
   a.draw = nullptr;
@@ -547,10 +547,11 @@ extern "C" int sf_set_render_order_hint(sf_batch* b, const uint64_t* words_host,
 }
 
 #ifdef SF_STAMPS
+extern "C" int sf_debug_slots(void) { return SF_STAMP_SLOTS; }  // stamps per wave: the width of sf_debug_read's rows
 extern "C" int sf_debug_read(sf_batch* b, unsigned long long* host) {
   DeviceGuard guard(b->device);
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host, b->args.dbg, (size_t)(b->args.lanes / 64) * 16 * sizeof(unsigned long long),
+  HIP_TRY(hipMemcpy(host, b->args.dbg, (size_t)(b->args.lanes / 64) * SF_STAMP_SLOTS * sizeof(unsigned long long),
                     hipMemcpyDeviceToHost));
   return SF_OK;
 }

@@ -65,8 +65,9 @@
 #define SF_SPLIT 1 /* 1: batches up to 65 536 envs (at most one games' wave per SIMD) step by split launches (sf_step_kernel, BLKP = 1000 + BLK): A/B 4 096 envs 5.48 -> 5.29 us, 32 768: 6.11 -> 5.89, 65 536: 6.51 -> 6.39; 0: never; 2: every batch the instantiation can serve (tests) */
 #endif
 #ifndef SF_MROWS
-#define SF_MROWS 3 /* rows of the tile's missile pool (64 entries each) loaded up front with the lane's chunks; more live
-                      missiles than that (> 192 in 64 envs; random play averages 104) take the dependent-load loop */
+#define SF_MROWS 3 /* rows of the tile's missile pool (64 entries each) loaded up front with the lane's chunks (a split launch's
+                      missile wave: those of them the pool reaches); more live missiles than that (> 192 in 64 envs; random
+                      play averages 104) take the dependent-load loop */
 #endif
 #ifndef SF_SPF
 #define SF_SPF 6 /* shell slots prefetched, one at a time (A/B at 65 536 envs with the missile pool: pairs 6.82 us per launch, singles 6.75) */
@@ -381,7 +382,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     sf_buf_st128<kStAux>(__builtin_bit_cast(u4_t, v), rs, p ? o.o16 + extra : SF_OOB, goff);
   };
 #ifdef SF_STAMPS
-  unsigned long long stamp_[16] = {};
+  unsigned long long stamp_[SF_STAMP_SLOTS] = {};
   stamp_[12] = __builtin_amdgcn_s_memrealtime();
 #endif
   SF_STAMP(0, false);
@@ -414,6 +415,12 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     // instructions take the same issue slots.  Issue priority for the first wave and a later start for the pool's loads
     // changed nothing measurable; starting them 1 500 cycles later made the games wait; asked for without waiting for the
     // pool's count: nothing either (tools/ab.py, NOTES.md, profiles/r04_split_ab.txt, profiles/closed_switches.md).
+    // The games' wave does not wait for this one: its poll of the `done` word (stamps 16 -> 17 of the instrument build)
+    // takes 280 cycles at the median, 316 at p90 and 276-336 on the ten slowest waves of a launch, which is the price of
+    // the poll itself (one LDS read and its hand-off to the scalar unit) with the word already set.  Doing the tick's
+    // independent tail in front of that poll -- key timers, computeExtra, eleven features of the row -- therefore has
+    // nothing to hide in and measured +0.09 us per launch; the ship's two chunks stored there as well: +-0
+    // (profiles/step_handover_fill.md).
     if (tid_all >= (unsigned)BLK) {  // wave-uniform
       // the pool's count rides in every lane's misc chunk: lane 0's word, by a scalar load
       const unsigned n_word = *reinterpret_cast<const __attribute__((address_space(4))) unsigned*>(
@@ -432,13 +439,28 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
 #pragma unroll
       for (int k = 0; k < kTrigPieces; k++) reinterpret_cast<d2_t*>(lds)[cpi0[k]] = cst0[k];
       if (lane < 4u) hflags[lane] = 0u;
+      asm volatile("" ::: "memory");
+      // A row the pool does not reach is not asked for at all: the count is scalar, the test a scalar branch (no exec
+      // mask), and an instruction that moves no bytes still takes its turn at the CU's one address unit (random play keeps
+      // 2 rows of the 3 in use: 8 instructions less per CU and tick; A/B at 65 536 envs 6.40 -> 6.28 us per launch,
+      // profiles/step_handover_fill.md).  Behind the table's LDS write, as before: the compiler cannot count loads it does
+      // not see issued, so a wait for the table placed behind them would be a wait for them too, in front of the barrier.
+      // (a skipped row's position registers are never used: m_row runs behind the same test; its meta word is 0, so the
+      //  heading looked up for it below is entry 0 of the table)
 #pragma unroll
       for (int r = 0; r < SF_MROWS; r++) {
-        const bool in_ = 64u * r + lane < m_live;
-        prow[r] = __builtin_bit_cast(d2_t, __builtin_amdgcn_raw_buffer_load_b128(rs, in_ ? o.o16 : SF_OOB, SF_GOFF(missile_pos, r), 0));
-        pmeta[r] = __builtin_amdgcn_raw_buffer_load_b32(rs, in_ ? o.o4 : SF_OOB, SF_GOFF(missile_meta, r), 0);
+        asm volatile("" : "=v"(prow[r].x), "=v"(prow[r].y));
+        pmeta[r] = 0u;
+        if (m_live > 64u * r) {
+          const bool in_ = 64u * r + lane < m_live;
+          prow[r] = __builtin_bit_cast(d2_t, __builtin_amdgcn_raw_buffer_load_b128(rs, in_ ? o.o16 : SF_OOB, SF_GOFF(missile_pos, r), 0));
+          pmeta[r] = __builtin_amdgcn_raw_buffer_load_b32(rs, in_ ? o.o4 : SF_OOB, SF_GOFF(missile_meta, r), 0);
+        }
       }
       __syncthreads();  // (the workgroup's one barrier: the cos/sin table is in LDS, the hand-over words are zero)
+      // (the rows' first use stays behind the barrier: moved in front of it, it is the wait for them the line above avoids)
+#pragma unroll
+      for (int r = 0; r < SF_MROWS; r++) asm volatile("" : "+v"(pmeta[r]));
       const double* trig = lds;
       d2_t pcs[SF_MROWS];
 #pragma unroll
@@ -995,9 +1017,11 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     };
     if constexpr (SPLIT) {  // the tile's missile wave did all of that: wait for its word
       unsigned dw, spins = 0u;
+      SF_STAMP(16, false);
       while (!((dw = (unsigned)__builtin_amdgcn_readfirstlane((int)hflags[1])) >> 31) && ++spins < kSpinLimit) __builtin_amdgcn_s_sleep(1);
       if (spins >= kSpinLimit && lane == 0u) atomicAdd(&a.acc[SF_ACC_HANDOVER], 1ull);
       asm volatile("" ::: "memory");
+      SF_STAMP(17, false);
       wp = dw & 0x7FFFFFFFu;
     } else {
 #pragma unroll
@@ -1270,9 +1294,9 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   stamp_[13] = __builtin_amdgcn_s_memrealtime();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   if (a.dbg != nullptr && (tid & 63) == 0) {
-    unsigned long long* d = a.dbg + (size_t)(i >> 6) * 16;
+    unsigned long long* d = a.dbg + (size_t)(i >> 6) * SF_STAMP_SLOTS;
 #pragma unroll
-    for (int k = 0; k < 16; k++) d[k] = stamp_[k];
+    for (int k = 0; k < SF_STAMP_SLOTS; k++) d[k] = stamp_[k];
   }
 #endif
 }

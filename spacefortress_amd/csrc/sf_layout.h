@@ -271,6 +271,10 @@ struct Score {
 };
 }  // namespace sfc
 
+// SF_STAMPS diagnostic builds (tools/stamps.py): clock stamps per wave (16, 17: a split launch's games' wave in front of
+// and behind its poll of the missile wave's word)
+#define SF_STAMP_SLOTS 18
+
 // Everything the kernels need that is uniform across lanes; passed by value (kernarg -> SGPRs).
 struct SfKernelArgs {
   unsigned char* state;      // base of the tiled state block
@@ -286,7 +290,7 @@ struct SfKernelArgs {
   int obs_type, obs_f64, real_shell_count, obs_dim, auto_reset;
   // episode accumulators / error counter (device)
   unsigned long long* acc;   // SF_ACC_WORDS words: the episode statistics, then the two sticky error counters
-  unsigned long long* dbg;   // SF_STAMPS diagnostic builds only: [wave][16] clock stamps; else null
+  unsigned long long* dbg;   // SF_STAMPS diagnostic builds only: [wave][SF_STAMP_SLOTS] clock stamps; else null
   unsigned* events;          // optional per-tick event bitmask output (SF_EV_*), [n_steps][n_envs]; else null
   // optional trainer bookkeeping of rl/train.py:82-88 + rollouts.insert (sf_step_record): reward as float and
   // mask = 1 - done for this tick ([n_steps][n_envs]); episode / final reward accumulators and the action as

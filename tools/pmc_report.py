@@ -55,7 +55,8 @@ def main():
     write_factor = sum(b for _, b, m in cw) / sum(m for _, b, m in cw)
     lanes = (a.envs + 255) // 256 * 256  # only the launches of THIS workload (bench.py has legs at other sizes), one tick each
     one_tick = re.compile(r"sf_step_kernel<\w+, \w+, false\b")  # <AUTOTURN, SHAPED, FUSED = false, ...>
-    pick = lambda by: [v for (k, grid), v in by.items() if one_tick.search(k) and grid == lanes][0]
+    # (a split launch -- sf_step_kernel<..., 1000 + BLK> -- has a missile wave per tile: twice the threads)
+    pick = lambda by: [v for (k, grid), v in by.items() if one_tick.search(k) and grid in (lanes, 2 * lanes)][0]
     step_f, step_w = pick(fe), pick(wr)
     fetch_kib = sum(step_f) / len(step_f)
     write_kib = sum(step_w) / len(step_w)

@@ -20,15 +20,15 @@ DIAG = os.path.join(ROOT, "build", "diag", "libsfmi_stamps.so")
 
 
 def build(lite=False):
+    """The diagnostic build, source by source with the product's own flags (tools/variant.py)."""
     global DIAG
     if lite:
         DIAG = DIAG.replace("_stamps.so", "_stamps_lite.so")
     os.makedirs(os.path.dirname(DIAG), exist_ok=True)
-    csrc = os.path.join(ROOT, "spacefortress_amd", "csrc")
-    B = __import__("spacefortress_amd.build", fromlist=["SOURCES"])
-    cmd = ["/opt/rocm/bin/hipcc"] + B.FLAGS + ["-DSF_STAMPS"] + (["-DSF_STAMPS_LITE"] if lite else []) + [
-        os.path.join(csrc, f) for f in B.SOURCES] + ["-o", DIAG]
-    subprocess.check_call(cmd)
+    name = "stamps_lite" if lite else "stamps"
+    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "variant.py"), name, "-DSF_STAMPS"] +
+                          (["-DSF_STAMPS_LITE"] if lite else []))
+    os.replace(os.path.join(ROOT, "build", "abl", "libsfmi_%s.so" % name), DIAG)
 
 
 def main():
@@ -62,7 +62,9 @@ def main():
     torch.cuda.synchronize()
     L = _lib.lib()
     n_waves = (a.envs + 255) // 256 * 4
-    buf = np.zeros((n_waves, 16), np.uint64)
+    slots = L.sf_debug_slots()  # SF_STAMP_SLOTS of the library that is loaded (sf_layout.h)
+    assert slots >= 18, "this script reads stamps 0..17; the library has %d" % slots
+    buf = np.zeros((n_waves, slots), np.uint64)
     L.sf_debug_read.argtypes = [C.c_void_p, C.c_void_p]
     assert L.sf_debug_read(env._h, buf.ctypes.data_as(C.c_void_p)) == 0
     if a.lite:
@@ -89,6 +91,11 @@ def main():
               "reward/done/info stores %d | trainer epilogue %d" % tuple(np.median(np.diff(seq, axis=1), axis=0)))
     print("  %-45s %7.0f %7.0f   p99 %.0f  max %.0f" % ("wave total", np.median(tot), np.percentile(tot, 90),
                                                    np.percentile(tot, 99), tot.max()))
+    if buf[:, 16].any():  # split launches: the games' wave's poll for the missile wave's word (stamps 16 -> 17)
+        hw = (buf[:, 17] - buf[:, 16]).astype(np.int64)
+        print("  hand-over wait (poll of the missile wave's word): median %d  p90 %d  max %d; on the ten slowest waves: %s" % (
+            np.median(hw), np.percentile(hw, 90), hw.max(), " ".join("%d" % x for x in hw[np.argsort(tot)[-10:]])))
+        print("  shells' end -> poll (what sits in front of the wait): median %d" % np.median((buf[:, 16] - buf[:, 5]).astype(np.int64)))
     slow = np.argsort(tot)[-8:]
     print("  slowest waves, cycles per phase:")
     for w in slow:
