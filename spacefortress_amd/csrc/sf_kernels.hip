@@ -651,7 +651,11 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   const double* trig = lds;
   SF_STAMP(3, false);
 
-  unpack_lane_late(late, L);  // names only: the wait for the late set sits at the first real use
+  // A fused launch unpacks the late set here, once, in front of its tick loop.  One tick per launch unpacks it behind the
+  // two bearings (below): unpacked here, the sign extensions of the key timers -- pure ALU on the loaded words -- are
+  // scheduled right behind the respawn, and the wait they bring (the whole late set's round trip but for the score chunk,
+  // some eighty instructions after its issue) stands in front of the ship and both atan2s instead of under them.
+  if (FUSED) unpack_lane_late(late, L);
   const int n_iter = FUSED ? n_steps : 1;
   for (int step = 0; step < n_iter; step++) {
   int act = (XTRA && act_type == SF_ACT_SAMPLED) ? act_sampled : act_next;
@@ -783,6 +787,14 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   // the two bearings the rest of the tick and the observation need, side by side (ILP)
   double a_pos = sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x, lds + kLdsAtab);
   double a_vel = sf_atan2_core(L.vy, L.vx, lds + kLdsAtab);
+  if (!FUSED) {
+    // the late set's first use, pinned HERE: the timers' words pass through an empty asm together with the two bearings, so
+    // nothing that reads them can be scheduled in front of the atan2s, and the set's wait (vmcnt counts only the score chunk
+    // behind it) has the key / ship / bearing arithmetic to arrive under.  A/B at 65 536 envs: 6.38 -> 6.25 us per launch
+    // in loop launches, 6.43 -> 6.32 in graph launches (profiles/step_first_burst.md)
+    asm volatile("" : "+v"(a_pos), "+v"(a_vel), "+v"(late.ta.x), "+v"(late.ta.y), "+v"(late.ta.z), "+v"(late.ta.w));
+    unpack_lane_late(late, L);
+  }
 
   // ---- updateFortress (SRC/game.cpp:194-216)
   int new_s_slot = -1;
