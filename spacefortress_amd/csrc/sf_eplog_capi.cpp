@@ -1,34 +1,19 @@
 // sf_eplog_capi.cpp -- C ABI of the device-side episode log (include/sfmi.h, sf_episode_log.hip).
-#include <string.h>
+#include <memory>
 
-#include "sf_internal.h"
+#include "sf_batch.h"
 
 struct sf_eplog {
-  SfEplogArgs a;
-  int device;
+  SfEplogArgs a{};  // (raw pointers into the buffers below: what the kernels get)
+  int device = 0;
+  DevBuf<int4> acc;
+  DevBuf<sf_episode_record> ring;
+  DevBuf<unsigned long long> hist;
+  DevBuf<SfEplogHeader> hdr;
+  DevBuf<uint32_t> counts, offs;
 };
 
 namespace {
-#define HIP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      sf_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return SF_ERR_HIP;                                                               \
-    }                                                                                  \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool changed = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() {
-    if (changed) (void)hipSetDevice(prev);
-  }
-};
-
 size_t n_cells(const sf_eplog* h) { return (size_t)SF_EPLOG_ROWS * (size_t)((h->a.n + 255) / 256); }
 }  // namespace
 
@@ -50,48 +35,38 @@ extern "C" int sf_eplog_create(int n_envs, int64_t capacity, int hist_lo, int hi
     return SF_ERR_ARG;
   }
   DeviceGuard guard(device);
-  sf_eplog* h = new sf_eplog();
-  memset(h, 0, sizeof(*h));
+  std::unique_ptr<sf_eplog> owner(new sf_eplog());  // (behind the guard: an error return frees what it holds)
+  sf_eplog* const h = owner.get();
   h->device = device;
   h->a.n = n_envs;
   h->a.fire_action = fire_action;
   h->a.bins = hist_bins;
   h->a.hist_lo = hist_lo;
   h->a.capacity = (unsigned long long)capacity;
-#define TRY_FREE(expr)                                                                 \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      sf_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      sf_eplog_destroy(h);                                                             \
-      return SF_ERR_HIP;                                                               \
-    }                                                                                  \
-  } while (0)
-  TRY_FREE(hipMalloc((void**)&h->a.acc, sizeof(int4) * (size_t)n_envs));
-  TRY_FREE(hipMalloc((void**)&h->a.ring, sizeof(sf_episode_record) * (size_t)capacity));
-  TRY_FREE(hipMalloc((void**)&h->a.hist, sizeof(unsigned long long) * (size_t)hist_bins));
-  TRY_FREE(hipMalloc((void**)&h->a.hdr, sizeof(SfEplogHeader)));
-  TRY_FREE(hipMalloc((void**)&h->a.counts, sizeof(uint32_t) * n_cells(h)));
-  TRY_FREE(hipMalloc((void**)&h->a.offs, sizeof(uint32_t) * n_cells(h)));
-  TRY_FREE(hipMemset(h->a.acc, 0, sizeof(int4) * (size_t)n_envs));
-  TRY_FREE(hipMemset(h->a.ring, 0, sizeof(sf_episode_record) * (size_t)capacity));
-  TRY_FREE(hipMemset(h->a.hist, 0, sizeof(unsigned long long) * (size_t)hist_bins));
-  TRY_FREE(hipMemset(h->a.hdr, 0, sizeof(SfEplogHeader)));
-  TRY_FREE(hipDeviceSynchronize());
-#undef TRY_FREE
-  *out = h;
+  HIP_TRY(h->acc.alloc((size_t)n_envs));
+  HIP_TRY(h->ring.alloc((size_t)capacity));
+  HIP_TRY(h->hist.alloc((size_t)hist_bins));
+  HIP_TRY(h->hdr.alloc(1));
+  HIP_TRY(h->counts.alloc(n_cells(h)));
+  HIP_TRY(h->offs.alloc(n_cells(h)));
+  h->a.acc = h->acc.get();
+  h->a.ring = h->ring.get();
+  h->a.hist = h->hist.get();
+  h->a.hdr = h->hdr.get();
+  h->a.counts = h->counts.get();
+  h->a.offs = h->offs.get();
+  HIP_TRY(hipMemset(h->a.acc, 0, sizeof(int4) * (size_t)n_envs));
+  HIP_TRY(hipMemset(h->a.ring, 0, sizeof(sf_episode_record) * (size_t)capacity));
+  HIP_TRY(hipMemset(h->a.hist, 0, sizeof(unsigned long long) * (size_t)hist_bins));
+  HIP_TRY(hipMemset(h->a.hdr, 0, sizeof(SfEplogHeader)));
+  HIP_TRY(hipDeviceSynchronize());
+  *out = owner.release();
   return SF_OK;
 }
 
 extern "C" int sf_eplog_destroy(sf_eplog* h) {
   if (!h) return SF_OK;
-  DeviceGuard guard(h->device);
-  if (h->a.acc) (void)hipFree(h->a.acc);
-  if (h->a.ring) (void)hipFree(h->a.ring);
-  if (h->a.hist) (void)hipFree(h->a.hist);
-  if (h->a.hdr) (void)hipFree(h->a.hdr);
-  if (h->a.counts) (void)hipFree(h->a.counts);
-  if (h->a.offs) (void)hipFree(h->a.offs);
+  DeviceGuard guard(h->device);  // (in scope while the buffers are freed)
   delete h;
   return SF_OK;
 }

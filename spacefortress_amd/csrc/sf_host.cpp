@@ -1,6 +1,7 @@
 // sf_host.cpp -- host-side constants of the path: presets, action tables, the libc spawn
-// sequence, the integer-degree trig table, hexagon edges.  No HIP calls in this file, so
-// everything here is exercised by the CPU test-suite through the C ABI.
+// sequence, the integer-degree trig table, hexagon edges; and the host-only checks of the C ABI: a preset
+// against the constants compiled into the kernels, sf_set_field's value ranges.  No HIP calls in this file, so
+// everything here is exercised by the CPU test-suite through the C ABI or sf_internal.h.
 //
 // SRC = python/spacefortress/src, ENV = python/spacefortress.gym/spacefortress/gym/envs/ssf_env.py
 // of the reference.
@@ -272,4 +273,80 @@ void sf_host_fill_consts(const sf_preset& p, double* c) {
   hex_edges(p.big_hex, c + SF_LDS_BIGHEX);
   hex_edges(p.small_hex, c + SF_LDS_SMALLHEX);
   for (int k = 0; k < SF_ATAB_DOUBLES; k++) c[SF_CONST_ATAB + k] = k <= 16 ? atan((double)k / 16.0) : 0.0;
+}
+
+// Everything of baseConfig (SRC/configs.cpp:3-49) but the start velocity is identical in the four presets and is compiled
+// into the kernels (namespace sfc); the scoring triple is the SHAPED template argument.  True if `preset`, with the block
+// sf_host_fill_consts made of it, agrees with what was compiled in.
+bool sf_preset_compiled_in(const sf_preset& preset, const double* consts) {
+  const double rm = (double)(preset.missile_radius + preset.fortress_radius);
+  const double rs = (double)(preset.shell_radius + preset.ship_radius);
+  const bool same =
+      preset.width == (int)sfc::width_d && preset.height == (int)sfc::height_d &&
+      preset.game_time == sfc::game_time && preset.sector_size == sfc::sector_size &&
+      preset.lock_time == sfc::lock_time && preset.vuln_time == sfc::vuln_time &&
+      preset.vuln_threshold == sfc::vuln_threshold && preset.explode_duration == sfc::explode_duration &&
+      preset.turn_speed == sfc::turn_speed && preset.missile_speed == sfc::missile_speed &&
+      preset.shell_speed == sfc::shell_speed && preset.ship_accel == sfc::ship_accel &&
+      rm * rm == sfc::missile_hit_r2 && rs * rs == sfc::shell_hit_r2 &&
+      (double)preset.small_hex == sfc::ndist_a &&
+      ((double)preset.big_hex - (double)preset.small_hex) / 2.0 == sfc::ndist_b && preset.miss_penalty == 0 &&
+      (preset.shaped ? (preset.missile_penalty == 0.05 && preset.ship_death_penalty == 1 && preset.destroy_fortress == 1)
+                     : (preset.missile_penalty == 2.0 && preset.ship_death_penalty == 100 &&
+                        preset.destroy_fortress == 100));
+#define SF_E(nx, ny, px, py) nx, ny, px, py,
+  const double compiled_hex[48] = {SF_BIG_HEX_EDGES(SF_E) SF_SMALL_HEX_EDGES(SF_E)};
+#undef SF_E
+  const bool same_hex = preset.big_hex == 200 && preset.small_hex == 40 &&
+                        memcmp(compiled_hex, consts + SF_LDS_BIGHEX, sizeof(compiled_hex)) == 0;
+  return same && same_hex;
+}
+
+// sf_set_field's range checks.  The packed fields live in bit fields of packed words (sf_layout.h: SF_W_*): a value that does
+// not fit is an error, not a silent truncation (the reference keeps plain ints, SRC/game.hh:29-43).  `host` is the field as
+// the caller passes it, [count][n_envs]; fields without such a limit pass.
+int sf_field_values_fit(int field, const void* host, long n) {
+  const sfl::FieldMeta& m = sfl::kFields[field];
+  auto fits = [](long x, int bits, int sgn) { return sgn ? (x >= -(1l << (bits - 1)) && x < (1l << (bits - 1))) : (x >= 0 && x < (1l << bits)); };
+  if (m.kind == SF_FK_BITS) {
+    const int32_t* v = (const int32_t*)host;
+    const sfl::BitField bf = sfl::bit_field(field);
+    const bool uns32 = m.elem_size == 4 && !bf.is_signed;
+    for (long e = 0; e < n; e++) {
+      const long x = uns32 ? (long)(uint32_t)v[e] : (long)v[e];
+      if (!fits(x, bf.bits, bf.is_signed)) {
+        sf_set_error("sf_set_field(%s): value %ld of env %ld does not fit the field's %d bits", m.name, x, e, bf.bits);
+        return SF_ERR_ARG;
+      }
+    }
+  } else if (m.kind == SF_FK_STATS) {
+    const int32_t* v = (const int32_t*)host;
+    for (int k = 0; k < SF_NSTAT; k++)
+      for (long e = 0; e < n; e++)
+        if (!fits(v[(long)k * n + e], sfl::kStatBits[k], 0)) {
+          sf_set_error("sf_set_field(stats): stats[%d] = %d of env %ld does not fit its %d bits", k, v[(long)k * n + e], e,
+                       sfl::kStatBits[k]);
+          return SF_ERR_ARG;
+        }
+    for (long e = 0; e < n; e++)
+      if (v[3 * n + e] != v[e] + v[n + e] + v[2 * n + e]) {  // killShip's three call sites (SRC/game.cpp:339,345,413)
+        sf_set_error("sf_set_field(stats): ship deaths (stats[3] = %d) of env %ld must be the sum of the big-hex, small-hex "
+                     "and shell deaths (%d): it is not stored separately", v[3 * n + e], e, v[e] + v[n + e] + v[2 * n + e]);
+        return SF_ERR_ARG;
+      }
+  } else if (field == SF_F_missile_angle) {
+    // int16 on this side, 9 bits in a pool entry (sf_layout.h: SF_MM_*): the same rule -- pool_rebuild would keep the low
+    // nine bits, and -1 would fly as heading 511, past the 360 entries of the trig table
+    const int16_t* v = (const int16_t*)host;
+    const int max_heading = (int)SF_MM_ANGLE(~0u);
+    for (int s = 0; s < SF_NSLOT; s++)
+      for (long e = 0; e < n; e++) {
+        const int x = v[(long)s * n + e];
+        if (x < 0 || x > max_heading) {
+          sf_set_error("sf_set_field(missile_angle): heading %d of env %ld, slot %d does not fit a pool entry's 9 bits", x, e, s);
+          return SF_ERR_ARG;
+        }
+      }
+  }
+  return SF_OK;
 }

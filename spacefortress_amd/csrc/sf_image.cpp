@@ -4,7 +4,8 @@
 //     scan converter (sf_cairo_host.cpp), for any geometry;
 //   * the live fortress's coverage at its 36 headings (one cairo_stroke of four lines: SRC/draw.cpp:238-242), the explosion's
 //     arc constants;
-//   * the INTER_AREA resampling tables of cv2.resize(frame, (84, 84)) (rl/envs.py:29).
+//   * the INTER_AREA resampling tables of cv2.resize(frame, (84, 84)) (rl/envs.py:29), and the two device layouts of them with
+//     the checks of what the frame kernels assume.
 // cv2 (OpenCV) is a dependency of the reference that is not vendored in /root/reference and not
 // installed in this image; the table follows OpenCV's published algorithm (modules/imgproc/src/
 // resize.cpp, computeResizeAreaTab, the general non-integer-scale area path).
@@ -139,6 +140,70 @@ extern "C" int sf_resize_area_tab(int ssize, int dsize, int32_t* first, int32_t*
     if (fsx2 - sx2 > 1e-3) a[k++] = (float)(fmin(fmin(fsx2 - sx2, 1.0), cell) / cell);
     first[dx] = f;
     count[dx] = k;  // <= 3 for ssize < 2*dsize, <= 4 for ssize < 3*dsize
+  }
+  return SF_OK;
+}
+
+// The default geometry's taps (90 -> 84 columns, then 92 -> 84 rows) in the device layout of sf_raster.h: per destination
+// (first, three weights).  Refused unless they have the structure the frame kernel assumes.
+int sf_area_tabs_default(uint32_t* tabs) {
+  memset(tabs, 0, SF_TAB_WORDS * sizeof(uint32_t));
+  const int ssize[2] = {SF_IMG_W, SF_IMG_H};
+  bool ok = true;
+  for (int ax = 0; ax < 2; ax++) {
+    int32_t first[SF_OUT], count[SF_OUT];
+    float alpha[SF_OUT * 4];
+    sf_resize_area_tab(ssize[ax], SF_OUT, first, count, alpha);
+    for (int i = 0; i < SF_OUT; i++) {
+      // what the kernel's sparse resampling assumes: two column taps; <= three row taps; and the
+      // windows where its dirty-box arithmetic expects them (first in [i*s - 1, i*s], s = 15/14, 23/21)
+      const double lo = (double)i * ssize[ax] / SF_OUT;
+      ok = ok && count[i] <= (ax == 0 ? 2 : 3) && first[i] >= (int)floor(lo) - 1 && first[i] <= (int)floor(lo) &&
+           first[i] + count[i] <= ssize[ax];
+      uint32_t* t = &tabs[4 * (ax * SF_OUT + i)];
+      t[0] = (uint32_t)first[i];
+      memcpy(t + 1, alpha + 4 * i, 3 * sizeof(float));
+      // ... and that the taps repeat exactly (90 / 84 = 15 / 14, 92 / 84 = 23 / 21): the frame kernel keeps ONE period in
+      // LDS (sf_render.hip: resample_into)
+      const int P = ax == 0 ? 14 : 21, Q = ax == 0 ? 15 : 23;
+      if (i >= P)
+        ok = ok && first[i] == first[i - P] + Q && count[i] == count[i - P] &&
+             memcmp(alpha + 4 * i, alpha + 4 * (i - P), 3 * sizeof(float)) == 0;
+      // ... and what its exact dirty box relies on (sf_render.hip: out_box): a source cell s is read with a weight
+      // that is not zero only by the destinations floor(N s / D) ... ceil(N (s + 1) / D) - 1, N / D = 14/15, 21/23
+      const int N = ax == 0 ? 14 : 21, D = ax == 0 ? 15 : 23;
+      for (int j = 0; j < count[i]; j++) {
+        const int sc = first[i] + j;
+        if (alpha[4 * i + j] != 0.0f) ok = ok && i >= (sc * N) / D && i < ((sc + 1) * N + D - 1) / D;
+      }
+    }
+  }
+  if (!ok) {
+    sf_set_error("sf_create: INTER_AREA table does not have the structure the render kernel assumes");
+    return SF_ERR_ARG;
+  }
+  return SF_OK;
+}
+
+// ... and those of a w x h surface (sf_render_generic.hip): per destination (first, count, four weights, two pad)
+int sf_area_tabs_geom(int w, int h, uint32_t* tabs) {
+  memset(tabs, 0, 16 * SF_OUT * sizeof(uint32_t));
+  const int ssize[2] = {w, h};
+  for (int ax = 0; ax < 2; ax++) {
+    int32_t first[SF_OUT], count[SF_OUT];
+    float alpha[SF_OUT * 4];
+    const int rc = sf_resize_area_tab(ssize[ax], SF_OUT, first, count, alpha);
+    if (rc != SF_OK) return rc;
+    for (int i = 0; i < SF_OUT; i++) {
+      uint32_t* t = &tabs[8 * (ax * SF_OUT + i)];
+      t[0] = (uint32_t)first[i];
+      t[1] = (uint32_t)count[i];
+      memcpy(t + 2, alpha + 4 * i, 4 * sizeof(float));
+      if (first[i] < 0 || count[i] < 1 || count[i] > 4 || first[i] + count[i] > ssize[ax]) {
+        sf_set_error("sf_set_image_geometry: INTER_AREA table out of range");
+        return SF_ERR_ARG;
+      }
+    }
   }
   return SF_OK;
 }

@@ -107,7 +107,16 @@ hipError_t sf_launch_eplog_restart_where(const SfEplogArgs& a, const uint8_t* ma
 
 // sf_host.cpp (no HIP calls: usable and tested without a GPU)
 void sf_host_fill_consts(const sf_preset& p, double* consts /* SF_CONST_DOUBLES */);
+// does the preset, with sf_host_fill_consts' block of it, agree with the constants compiled into the kernels (sfc::, the hexagons)?
+bool sf_preset_compiled_in(const sf_preset& p, const double* consts);
+// sf_set_field's range checks of `host` = field [count][n_envs]: the packed bit fields, the 13 statistics and their sum rule,
+// the missile headings; SF_OK, or SF_ERR_ARG with the env (and slot) in the error text
+int sf_field_values_fit(int field, const void* host, long n_envs);
 void sf_set_error(const char* fmt, ...);
+// sf_image.cpp: the INTER_AREA taps in the two device layouts -- the default geometry's (SF_TAB_WORDS words, sf_raster.h;
+// refused unless they have the structure the frame kernel assumes) and a w x h surface's (16 * SF_OUT words, range-checked)
+int sf_area_tabs_default(uint32_t* tabs);
+int sf_area_tabs_geom(int w, int h, uint32_t* tabs);
 // sf_image.cpp: the score text's glyph atlas (sf_glyphs.h) -- the built-in one, a caller's, and the static background with
 // the score 0000000 of a given atlas baked in
 void sf_glyphs_default(SfGlyphAtlas* G);

@@ -127,6 +127,11 @@ enum SfFieldId {
 // after 32 767 ticks without an edge of its key (six episodes' worth; every new game zeroes it), `time` after 2^24 ms
 // (4.6 hours of game time without a new game: auto_reset off and a caller that never resets).
 // sf_get_field / sf_set_field see plain ints: SF_BITFIELDS says where each one lives.
+namespace sfl {
+// the widths of the 13 statistics in the table above, in `stats` order (ship deaths: the sum's) -- sf_set_field's range check
+constexpr int kStatBits[] = {8, 8, 8, 10, 16, 8, 16, 16, 16, 16, 16, 12, 12};
+static_assert(sizeof(kStatBits) / sizeof(kStatBits[0]) == SF_NSTAT, "one width per statistic");
+}  // namespace sfl
 #define SF_KEYCOUNT_BYTE 8
 #define SF_ST_KEY_FIRST 7 /* SF_ST_SHOTS */
 #define SF_ST_KEY_COUNT 4

@@ -1,40 +1,18 @@
 // sf_norm_capi.cpp -- C ABI of the device-side VecNormalize (include/sfmi.h, sf_normalize.hip).
-#include <stdlib.h>
-#include <string.h>
-
+#include <memory>
 #include <vector>
 
-#include "sf_internal.h"
+#include "sf_batch.h"
 
 struct sf_normalizer {
-  sf_normalizer_params p;
-  int parity;
-  double* d_ret;       // per-env discounted return (VecNormalize.ret)
-  double* d_partials;  // SF_NORM_GROUPS x 2 * (D + 1), then the ticket counter
-  double* d_stats[2];  // 2 * D + 4
+  sf_normalizer_params p{};
+  int parity = 0;
+  DevBuf<double> d_ret;       // per-env discounted return (VecNormalize.ret)
+  DevBuf<double> d_partials;  // SF_NORM_GROUPS x 2 * (D + 1), then the ticket counter
+  DevBuf<double> d_stats[2];  // 2 * D + 4
 };
 
 namespace {
-#define HIP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      sf_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return SF_ERR_HIP;                                                               \
-    }                                                                                  \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool changed = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() {
-    if (changed) (void)hipSetDevice(prev);
-  }
-};
-
 // A call that updates the statistics flips z->parity on the host: a captured graph would replay the launch with the
 // buffers of the capture, not of the replay (sfmi.h).  Such a call inside a capture is refused before anything is launched.
 int refuse_in_capture(const char* who, hipStream_t st) {
@@ -68,48 +46,33 @@ extern "C" int sf_normalizer_create(const sf_normalizer_params* p, sf_normalizer
     return SF_ERR_ARG;
   }
   DeviceGuard guard(p->device_id);
-  sf_normalizer* z = new sf_normalizer();
-  memset(z, 0, sizeof(*z));
+  std::unique_ptr<sf_normalizer> owner(new sf_normalizer());  // (behind the guard: an error return frees what it holds)
+  sf_normalizer* const z = owner.get();
   z->p = *p;
   // RunningMeanStd.__init__: mean 0, var 1, count 1e-4
   std::vector<double> st(n_stats(z), 0.0);
   for (int f = 0; f < p->obs_dim; f++) st[p->obs_dim + f] = 1.0;
   st[2 * p->obs_dim + 1] = 1.0;
   st[2 * p->obs_dim + 2] = st[2 * p->obs_dim + 3] = 1e-4;
-#define TRY_FREE(expr)                                                                 \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      sf_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      sf_normalizer_destroy(z);                                                        \
-      return SF_ERR_HIP;                                                               \
-    }                                                                                  \
-  } while (0)
-  TRY_FREE(hipMalloc((void**)&z->d_ret, sizeof(double) * p->n_envs));
-  TRY_FREE(hipMemset(z->d_ret, 0, sizeof(double) * p->n_envs));
+  HIP_TRY(z->d_ret.alloc(p->n_envs));
+  HIP_TRY(hipMemset(z->d_ret.get(), 0, sizeof(double) * p->n_envs));
   // rows of partial sums: SF_NORM_GROUPS from the stand-alone reduction, or one per wave of the step kernel
   // (sf_step_normalize; the batch is padded to whole workgroups of 256 envs)
   const size_t rows = (size_t)((p->n_envs + 255) / 256) * 4;
   const size_t prow = rows > SF_NORM_GROUPS ? rows : SF_NORM_GROUPS;
-  TRY_FREE(hipMalloc((void**)&z->d_partials, sizeof(double) * n_sums(z) * prow));
-  TRY_FREE(hipMemset(z->d_partials, 0, sizeof(double) * n_sums(z) * prow));
+  HIP_TRY(z->d_partials.alloc(n_sums(z) * prow));
+  HIP_TRY(hipMemset(z->d_partials.get(), 0, sizeof(double) * n_sums(z) * prow));
   for (int k = 0; k < 2; k++) {
-    TRY_FREE(hipMalloc((void**)&z->d_stats[k], sizeof(double) * n_stats(z)));
-    TRY_FREE(hipMemcpy(z->d_stats[k], st.data(), sizeof(double) * n_stats(z), hipMemcpyHostToDevice));
+    HIP_TRY(z->d_stats[k].alloc(n_stats(z)));
+    HIP_TRY(hipMemcpy(z->d_stats[k].get(), st.data(), sizeof(double) * n_stats(z), hipMemcpyHostToDevice));
   }
-#undef TRY_FREE
-  *out = z;
+  *out = owner.release();
   return SF_OK;
 }
 
 extern "C" int sf_normalizer_destroy(sf_normalizer* z) {
   if (!z) return SF_OK;
-  DeviceGuard guard(z->p.device_id);
-  if (z->d_ret) (void)hipFree(z->d_ret);
-  if (z->d_partials) (void)hipFree(z->d_partials);
-  for (int k = 0; k < 2; k++) {
-    if (z->d_stats[k]) (void)hipFree(z->d_stats[k]);
-  }
+  DeviceGuard guard(z->p.device_id);  // (in scope while the buffers are freed)
   delete z;
   return SF_OK;
 }
@@ -132,9 +95,9 @@ extern "C" int sf_normalize(sf_normalizer* z, const void* obs_dev, void* obs_out
     if (rc != SF_OK) return rc;
   }
   HIP_TRY(sf_launch_normalize(z->p.ob ? obs_dev : nullptr, z->p.ob ? obs_out_dev : nullptr, z->p.obs_f64,
-                              z->p.ret ? reward_dev : nullptr, z->p.ret ? reward_out_dev : nullptr, z->d_ret, z->p.n_envs,
+                              z->p.ret ? reward_dev : nullptr, z->p.ret ? reward_out_dev : nullptr, z->d_ret.get(), z->p.n_envs,
                               z->p.obs_dim, z->p.gamma, z->p.epsilon, z->p.clipob, z->p.cliprew, do_ob, do_ret,
-                              z->d_partials, z->d_stats[k], z->d_stats[k ^ 1], (hipStream_t)stream));
+                              z->d_partials.get(), z->d_stats[k].get(), z->d_stats[k ^ 1].get(), (hipStream_t)stream));
   if (do_ob || do_ret) z->parity = k ^ 1;
   return SF_OK;
 }
@@ -142,9 +105,9 @@ extern "C" int sf_normalize(sf_normalizer* z, const void* obs_dev, void* obs_out
 extern "C" int sf_normalizer_get_state(sf_normalizer* z, double* host, double* ret_host, void* stream) {
   if (!z || !host) return SF_ERR_ARG;
   DeviceGuard guard(z->p.device_id);
-  HIP_TRY(hipMemcpyAsync(host, z->d_stats[z->parity], sizeof(double) * n_stats(z), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipMemcpyAsync(host, z->d_stats[z->parity].get(), sizeof(double) * n_stats(z), hipMemcpyDeviceToHost, (hipStream_t)stream));
   if (ret_host)
-    HIP_TRY(hipMemcpyAsync(ret_host, z->d_ret, sizeof(double) * z->p.n_envs, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(ret_host, z->d_ret.get(), sizeof(double) * z->p.n_envs, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return SF_OK;
 }
@@ -152,9 +115,9 @@ extern "C" int sf_normalizer_get_state(sf_normalizer* z, double* host, double* r
 extern "C" int sf_normalizer_set_state(sf_normalizer* z, const double* host, const double* ret_host, void* stream) {
   if (!z || !host) return SF_ERR_ARG;
   DeviceGuard guard(z->p.device_id);
-  HIP_TRY(hipMemcpyAsync(z->d_stats[z->parity], host, sizeof(double) * n_stats(z), hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIP_TRY(hipMemcpyAsync(z->d_stats[z->parity].get(), host, sizeof(double) * n_stats(z), hipMemcpyHostToDevice, (hipStream_t)stream));
   if (ret_host)
-    HIP_TRY(hipMemcpyAsync(z->d_ret, ret_host, sizeof(double) * z->p.n_envs, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(z->d_ret.get(), ret_host, sizeof(double) * z->p.n_envs, hipMemcpyHostToDevice, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return SF_OK;
 }
@@ -179,14 +142,14 @@ extern "C" int sf_step_normalize(sf_batch* b, sf_normalizer* z, const void* acti
   int rows = 0;
   int rc = refuse_in_capture("sf_step_normalize", (hipStream_t)stream);
   if (rc != SF_OK) return rc;
-  rc = sf_step_with_norm_partials(b, actions_dev, act_type, obs_dev, reward_dev, done_dev, info_dev, z->d_partials,
-                                      z->p.ret ? z->d_ret : nullptr, z->p.gamma, &rows, stream);
+  rc = sf_step_with_norm_partials(b, actions_dev, act_type, obs_dev, reward_dev, done_dev, info_dev, z->d_partials.get(),
+                                      z->p.ret ? z->d_ret.get() : nullptr, z->p.gamma, &rows, stream);
   if (rc != SF_OK) return rc;
   const int k = z->parity;
   HIP_TRY(sf_launch_normalize_after_step(z->p.ob ? obs_dev : nullptr, z->p.ob ? obs_dev : nullptr, z->p.obs_f64,
                                          z->p.ret ? reward_dev : nullptr, z->p.ret ? reward_out_dev : nullptr, z->p.n_envs,
-                                         z->p.obs_dim, z->p.epsilon, z->p.clipob, z->p.cliprew, z->p.ob, z->p.ret, z->d_partials,
-                                         rows, z->d_stats[k], z->d_stats[k ^ 1], (hipStream_t)stream));
+                                         z->p.obs_dim, z->p.epsilon, z->p.clipob, z->p.cliprew, z->p.ob, z->p.ret, z->d_partials.get(),
+                                         rows, z->d_stats[k].get(), z->d_stats[k ^ 1].get(), (hipStream_t)stream));
   z->parity = k ^ 1;
   return SF_OK;
 }

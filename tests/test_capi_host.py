@@ -45,6 +45,20 @@ def test_binary_is_stamped_with_the_hash_of_its_sources(L):
     assert not sfbuild.needs_build()
 
 
+def test_build_id_covers_every_source_and_header():
+    """Every *.h of csrc/ is in build.py's HEADERS and every *.cpp / *.hip in SOURCES, and nothing else: a file the hash
+    does not read could change without changing sf_build_id() or triggering a rebuild."""
+    from spacefortress_amd import build as sfbuild
+
+    files = os.listdir(sfbuild.CSRC)
+    assert sorted(sfbuild.SOURCES) == sorted(f for f in files if f.endswith((".cpp", ".hip")))
+    assert len(set(sfbuild.SOURCES)) == len(sfbuild.SOURCES)
+    inside = [h for h in sfbuild.HEADERS if not os.path.isabs(h)]
+    assert sorted(inside) == sorted(f for f in files if f.endswith(".h"))
+    public = sorted(os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
+    assert sorted(h for h in sfbuild.HEADERS if os.path.isabs(h)) == public
+
+
 def test_no_wide_buffer_store_without_its_wait_state(L):
     """The shipped binary, disassembled: no 128-bit buffer store with an SGPR soffset whose next instruction overwrites
     its data (build.py: scan_wide_store_hazard -- the compiler does not cover that form, and with more than one wave on a
