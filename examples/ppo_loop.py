@@ -14,6 +14,12 @@ self-contained; the point is the data path: nothing crosses PCIe inside an itera
 once, the actor reads the current stack that step() returns and the minibatches are gathered as float32 by one launch each.
 
     python examples/ppo_loop.py --obs image --envs 1024 --steps 32 --iters 5
+
+--time-limit-bootstrap (features): every episode of this game ends by the clock, so `done` is a truncation; the rollout keeps
+each env's final observation and the returns bootstrap with the critic's value of it instead of 0 -- one more critic forward
+per update (DeviceRollout(time_limit_bootstrap=True), INTEGRATION.md "Episodes end by the clock").
+
+    python examples/ppo_loop.py --time-limit-bootstrap --envs 256 --steps 16 --iters 2
 """
 import argparse
 import os
@@ -113,13 +119,17 @@ def main():
     ap.add_argument("--gametype", default="autoturn")
     ap.add_argument("--ppo-epochs", type=int, default=4)
     ap.add_argument("--mini-batches", type=int, default=4)
+    ap.add_argument("--time-limit-bootstrap", action="store_true",
+                    help="features: bootstrap the returns at an episode's end with V(final observation) instead of 0")
     a = ap.parse_args()
     torch.manual_seed(0)
     if a.obs == "image":
+        if a.time_limit_bootstrap:
+            ap.error("--time-limit-bootstrap is for --obs features (image batches have no final-observation output)")
         return main_image(a)
     envs = SFVecNormalize(SFVecEnv(a.envs, gametype=a.gametype, spawn_stride=1))
     log = envs.venv.enable_episode_log()
-    ro = DeviceRollout(envs, a.steps)
+    ro = DeviceRollout(envs, a.steps, time_limit_bootstrap=a.time_limit_bootstrap)
     net = ActorCritic(envs.venv.obs_dim, envs.venv.n_actions).to(envs.device)
     opt = torch.optim.Adam(net.parameters(), lr=7e-4)
     ro.reset()
@@ -133,7 +143,9 @@ def main():
             ro.step(t, action, value_pred=value, action_log_prob=dist.log_prob(action).unsqueeze(1))
         with torch.no_grad():
             next_value = net(ro.observations[-1])[1]
-        ro.compute_returns(next_value, True, 0.99, 0.95)
+            # the critic's value of every env's final observation (normalised like the rest): used where masks == 0 only
+            final_value = net(ro.final_obs())[1] if a.time_limit_bootstrap else None
+        ro.compute_returns(next_value, True, 0.99, 0.95, final_value=final_value)
         adv = ro.returns[:-1] - ro.value_preds[:-1]
         adv = (adv - adv.mean()) / (adv.std() + 1e-5)
         for _ in range(a.ppo_epochs):

@@ -333,6 +333,27 @@ int sf_frame_stack_clear(uint8_t* stack_dev, size_t bytes_per_env, const uint8_t
 #define SF_EV_GAME_OVER 0x200000u       /* is_game_over() became true (the env is auto-reset unless SF_FLAG_NO_AUTO_RESET) */
 int sf_set_event_output(sf_batch* b, uint32_t* events_dev);
 
+/* ---- the finished game's LAST observation.  Every episode ends by the clock (done = time >= game_time,
+ *      SRC/game.cpp:487-489): `done` is a time-limit truncation, never a terminal state, and the auto-reset
+ *      replaces the finished env's observation row with the first one of its next game (rl/train.py:80).  A
+ *      trainer that bootstraps the target there with V(last observation) needs the row that was replaced --
+ *      gymnasium's `final_observation`.  Once a buffer is set, every stepping entry point (sf_step,
+ *      sf_step_sampled, sf_step_record, sf_step_normalize, sf_rollout, sf_rollout_sampled) writes, for each env
+ *      whose done flag it sets, the observation SSF_Env.step returned for that tick (ENV:246-253) to row
+ *      [env] of final_obs_dev, [n_envs][obs_dim] in the batch's observation type (float, or double with
+ *      SF_FLAG_OBS_F64; SF_FLAG_REAL_SHELL_COUNT applies, SF_FLAG_REF_RESET_OBS does not: this is no new game's
+ *      row), and writes NO other row: the rows of envs that have not finished keep what the caller left there.
+ *      A fused launch leaves an env's most recent finish inside the launch.  sf_reset and sf_reset_lanes never
+ *      write it: an abandoned game is no finished episode (the rule of sf_episode_stats).  sf_step_normalize
+ *      normalises obs_dev, not this buffer: its rows are raw (sf_normalize them, frozen).  Plain stream work:
+ *      capturable in a HIP graph.  final_obs_dev must be 16-byte aligned; NULL switches the output off.
+ *      SF_ERR_ARG, with the batch as it was, for an image batch (its route: SF_FLAG_NO_AUTO_RESET, read the
+ *      frames, sf_reset_lanes), for a SF_FLAG_NO_AUTO_RESET batch (a finished env's row of obs_dev already is
+ *      its last one) and for a batch without observation rows.  With the output set, a step is launched as the
+ *      step kernel's general instantiation, not as the split launch of the plain step (profiles/final_obs.md:
+ *      the price); with it NULL nothing changes. ---- */
+int sf_set_final_obs_output(sf_batch* b, void* final_obs_dev);
+
 /* Out-of-range actions are executed as NOOP and counted on the device; this reads and clears the
  * count (synchronises `stream`).  Returns SF_ERR_ACTION if any were seen since the last call. */
 int sf_check_actions(sf_batch* b, void* stream);
@@ -520,6 +541,17 @@ int sf_record_step_f32(int n, const float* reward_dev, const uint8_t* done_dev, 
                        int64_t* actions_out, void* stream);
 int sf_compute_returns(int num_steps, int n, const float* rewards, float* value_preds, const float* masks,
                        const float* next_value, float* returns, int use_gae, double gamma, double tau, void* stream);
+/* sf_compute_returns with the time limit's bootstrap: a zero in masks[t+1][i] is a truncation by the clock, and the
+ * target there is r + gamma * V(final observation), not r.  final_value float [n] = the critic's value of every env's
+ * row of sf_set_final_obs_output's buffer.  The result is, bit for bit, what sf_compute_returns gives on
+ * rewards2[t][i] = masks[t+1][i] == 0 ? rewards[t][i] + (float)gamma * final_value[i] : rewards[t][i]  (float32: one
+ * multiply, then one add); a select, so the final_value of an env that never finished -- its row was never written:
+ * anything, NaN included -- leaves no trace.  One value per env: a rollout in which an env finishes twice (only
+ * possible beyond max_ticks + 1 steps, or with clocks a caller set) uses the later observation's value for both.
+ * `rewards` is only read.  SF_ERR_ARG for a NULL final_value and for what sf_compute_returns refuses. */
+int sf_compute_returns_tl(int num_steps, int n, const float* rewards, float* value_preds, const float* masks,
+                          const float* next_value, const float* final_value, float* returns, int use_gae, double gamma,
+                          double tau, void* stream);
 
 /* ---- The image rollout storage with every frame kept ONCE.  The trainer stores the whole frame stack of every step
  *      (rl/train.py:38-41: obs_shape[0] * num_stack channels; :51-56,92-98: shift, `current_obs *= masks`, insert) and

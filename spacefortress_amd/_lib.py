@@ -148,6 +148,8 @@ SYMBOLS = {
     "sf_render_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "sf_frame_stack_clear": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     "sf_set_event_output": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "sf_set_final_obs_output": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "sf_compute_returns_tl": (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "sf_render": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sf_image_background": (C.c_int, [C.c_void_p]),
     "sf_image_background_geom": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),

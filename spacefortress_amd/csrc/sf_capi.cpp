@@ -475,6 +475,32 @@ extern "C" int sf_set_event_output(sf_batch* b, uint32_t* events_dev) {
   return SF_OK;
 }
 
+extern "C" int sf_set_final_obs_output(sf_batch* b, void* final_obs_dev) {
+  if (!b) return SF_ERR_ARG;
+  if (final_obs_dev != nullptr) {  // (switching it off is always possible)
+    if (sfb_is_image(b)) {
+      sf_set_error("sf_set_final_obs_output: image batches have no final-observation output; create the batch with "
+                   "SF_FLAG_NO_AUTO_RESET, read the finished envs' frames and restart them with sf_reset_lanes");
+      return SF_ERR_ARG;
+    }
+    if (!b->args.auto_reset) {
+      sf_set_error("sf_set_final_obs_output: a SF_FLAG_NO_AUTO_RESET batch never replaces an observation: the row a finished "
+                   "env's step wrote already is its last one (restart it with sf_reset_lanes)");
+      return SF_ERR_ARG;
+    }
+    if (b->args.obs_type == SF_OBS_NONE || b->args.obs_dim <= 0) {
+      sf_set_error("sf_set_final_obs_output: this batch has no observation rows");
+      return SF_ERR_ARG;
+    }
+    if (((uintptr_t)final_obs_dev & 15) != 0) {
+      sf_set_error("sf_set_final_obs_output: the buffer must be 16-byte aligned");
+      return SF_ERR_ARG;
+    }
+  }
+  b->args.final_obs = final_obs_dev;
+  return SF_OK;
+}
+
 extern "C" int sf_check_actions(sf_batch* b, void* stream) {
   if (!b) return SF_ERR_ARG;
   DeviceGuard guard(b->device);

@@ -330,6 +330,9 @@ __global__ __launch_bounds__(SF_BLOCK) void sf_reset_kernel(SfKernelArgs a, int 
 // XTRA = the launch may need what the plain VecEnv.step never does -- actions drawn in the kernel (SF_ACT_SAMPLED), the
 // played actions written out (a.act_out), the packed counters' overflow test of batches without auto-reset: three uniform
 // tests and their code, 0.07 us of a 6.5 us launch when they sit in the one kernel everybody runs (A/B, tools/ab.py)
+// FOBS = an XTRA launch that also writes the finished games' last observations (a.final_obs, sf_set_final_obs_output).  A flag
+// of its own: inside the XTRA instantiations the row's code cost them 4 to 8 VGPRs, and the 64-thread ones of autoturn a wave
+// of occupancy, with the output off (profiles/final_obs.md); so they stay what they were, instruction for instruction.
 // BLK = threads per workgroup (64, 128 or 256: one to four tiles).  256 is what the metric's batch wants (65 536 envs = 256
 // workgroups, one per CU, the cos/sin table staged once per four waves); a batch of 16 384 envs is 256 waves all the same, and
 // as 64 workgroups of four it leaves three CUs in four idle while the four waves of a CU share its address unit and LDS:
@@ -338,7 +341,7 @@ __global__ __launch_bounds__(SF_BLOCK) void sf_reset_kernel(SfKernelArgs a, int 
 // BLKP = 1000 + BLK is a SPLIT launch: BLK envs per workgroup and a second wave per tile that moves the tile's missile pool
 // while the first plays the 64 games (see "the tile's MISSILE wave" below); what sf_launch_step takes for the plain step of the
 // default observation of batches up to 65 536 envs (beyond, a SIMD has several games' waves to interleave anyway).
-template <bool AUTOTURN, bool SHAPED, bool FUSED, int OBSK, bool XTRA, int BLKP>
+template <bool AUTOTURN, bool SHAPED, bool FUSED, int OBSK, bool XTRA, int BLKP, bool FOBS = false>
 __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_step_kernel(unsigned char* state_p, const double* consts_p,
                                                           const void* actions, int n_envs_p, int act_type,
                                                           int32_t* reward_out, uint8_t* done_out, uint8_t* info_out,
@@ -353,6 +356,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   constexpr int BLK = SPLIT ? BLKP - 1000 : BLKP;  // envs per workgroup
   constexpr int NT = SPLIT ? 2 * BLK : BLK;        // threads per workgroup
   static_assert(!SPLIT || (!FUSED && OBSK == 1 && !XTRA), "the split launch exists for the plain step of the default observation");
+  static_assert(!FOBS || XTRA, "the final-observation output rides on the XTRA instantiations");
   constexpr int kTrigPieces = (SF_LDS_DOUBLES / 2 + NT - 1) / NT;
   // (the LDS map above, for BLK envs; a split launch's hand-over words sit between the atan table and the staging rows:
   //  the new missiles' (x, y) [BLK d2_t] and meta words [BLK], then four words per tile: fired, pool done | count, stores done)
@@ -1175,6 +1179,12 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
       atomicMin((long long*)&a.acc[6], (long long)ep_ret);
       atomicMax((long long*)&a.acc[7], (long long)ep_ret);
     }
+    // the finished game's last observation (a.final_obs: sf_set_final_obs_output): the row SSF_Env.step returned for this
+    // tick (ENV:246-253), from the state as it stands and the tick's own bearings, before the new game replaces both.  Once
+    // per 5 295 ticks and lane: plain stores straight to the row, no staging
+    if (FOBS && a.final_obs != nullptr) {  // uniform
+      if (real) write_obs_row(a, a.final_obs, i, L, compute_extras(a, L, a_pos, a_vel));
+    }
     // a new Game (ENV:163-178).  Its missiles are gone with it: the pool entries this lane still owns leave below
     new_game(a, L);
     a_pos = sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x);
@@ -1333,7 +1343,9 @@ hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, con
   // the default observation has its own instantiations (OBSK = 1): see write_features_f32
   const bool fast_obs = obs != nullptr && a.obs_type == 0 && !a.obs_f64 && vec_ok && a.n_envs % 64 == 0 &&
                         a.obs_dim == (autoturn ? 17 : 19) && !a.ref_reset_obs;
-  const bool xtra = act_type == SF_ACT_SAMPLED || a.act_out != nullptr || !a.auto_reset;
+  // (the final-observation output: the XTRA instantiations' FOBS twins, whatever else the launch asks for)
+  const bool fobs = a.final_obs != nullptr;
+  const bool xtra = act_type == SF_ACT_SAMPLED || a.act_out != nullptr || !a.auto_reset || fobs;
   // a split launch (sf_step_kernel: a missile wave per tile) where a tile's wave is alone on its SIMD otherwise
   // (SF_SPLIT 2, for tests: every batch it can serve)
   // (SFMI_FORCE_SPLIT=1 in the environment, for tests: every batch the instantiation can serve; =2 says so once on stderr)
@@ -1347,21 +1359,21 @@ hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, con
   const unsigned grid = (unsigned)(a.lanes / blk);
   size_t lds_bytes = (size_t)(SF_LDS_DOUBLES + blk + SF_ATAB_DOUBLES) * sizeof(double) + (size_t)blk * a.obs_dim * elem;
   if (split) lds_bytes += (size_t)(2 * blk + blk / 2 + blk / 32) * sizeof(double);
-#define SF_GO2(AT, SH, FU, OK, XT, BL)                                                                             \
-  hipLaunchKernelGGL((sf_step_kernel<AT, SH, FU, OK, XT, BL>), dim3(grid), dim3((BL) > 1000 ? 2 * ((BL) - 1000) : (BL)), lds_bytes, stream, a.state,    \
+#define SF_GO2(AT, SH, FU, OK, XT, BL, FO)                                                                            \
+  hipLaunchKernelGGL((sf_step_kernel<AT, SH, FU, OK, XT, BL, FO>), dim3(grid), dim3((BL) > 1000 ? 2 * ((BL) - 1000) : (BL)), lds_bytes, stream, a.state,    \
                      a.consts, actions, a.n_envs, act_type, reward, done, info, a, obs, vec_ok, n_steps)
-#define SF_GO1(AT, SH, FU, OK, XT)                                                                                 \
+#define SF_GO1(AT, SH, FU, OK, XT, FO)                                                                             \
   do {                                                                                                             \
-    if (FU || blk == SF_BLOCK) SF_GO2(AT, SH, FU, OK, XT, SF_BLOCK);                                               \
-    else if (blk == 128) SF_GO2(AT, SH, false, OK, XT, 128);                                                       \
-    else SF_GO2(AT, SH, false, OK, XT, 64);                                                                        \
+    if (FU || blk == SF_BLOCK) SF_GO2(AT, SH, FU, OK, XT, SF_BLOCK, FO);                                           \
+    else if (blk == 128) SF_GO2(AT, SH, false, OK, XT, 128, FO);                                                   \
+    else SF_GO2(AT, SH, false, OK, XT, 64, FO);                                                                    \
   } while (0)
 #if SF_SPLIT
 #define SF_GO_SPLIT(AT, SH)                                                                                        \
   if (split) {                                                                                                     \
-    if (blk == SF_BLOCK) SF_GO2(AT, SH, false, 1, false, 1256);                                                    \
-    else if (blk == 128) SF_GO2(AT, SH, false, 1, false, 1128);                                                    \
-    else SF_GO2(AT, SH, false, 1, false, 1064);                                                                    \
+    if (blk == SF_BLOCK) SF_GO2(AT, SH, false, 1, false, 1256, false);                                             \
+    else if (blk == 128) SF_GO2(AT, SH, false, 1, false, 1128, false);                                             \
+    else SF_GO2(AT, SH, false, 1, false, 1064, false);                                                             \
   } else
 #else
 #define SF_GO_SPLIT(AT, SH)
@@ -1369,9 +1381,11 @@ hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, con
 #define SF_GO(AT, SH, FU)                                                                                          \
   SF_GO_SPLIT(AT, SH)                                                                                              \
   if (fast_obs) {                                                                                                  \
-    if (xtra) SF_GO1(AT, SH, FU, 1, true); else SF_GO1(AT, SH, FU, 1, false);                                      \
+    if (fobs) SF_GO1(AT, SH, FU, 1, true, true);                                                                   \
+    else if (xtra) SF_GO1(AT, SH, FU, 1, true, false); else SF_GO1(AT, SH, FU, 1, false, false);                   \
   } else {                                                                                                         \
-    if (xtra) SF_GO1(AT, SH, FU, 0, true); else SF_GO1(AT, SH, FU, 0, false);                                      \
+    if (fobs) SF_GO1(AT, SH, FU, 0, true, true);                                                                   \
+    else if (xtra) SF_GO1(AT, SH, FU, 0, true, false); else SF_GO1(AT, SH, FU, 0, false, false);                   \
   }
   // the four presets of SRC/configs.cpp:51-89 are exactly (autoTurn) x (shaped scoring)
   const int sel = (autoturn ? 4 : 0) | (shaped ? 2 : 0) | (fused ? 1 : 0);

@@ -321,6 +321,11 @@ struct SfKernelArgs {
   // SF_FLAG_REF_RESET_OBS: the observation of a NEW game (sf_reset, the auto-reset of a finished lane) carries aim = vdir =
   // ndist = 0, what the reference's wrapper returns on fresh memory (Game::Game leaves mExtra unwritten, SRC/game.cpp:78)
   int ref_reset_obs;
+  // optional (sf_set_final_obs_output): the LAST observation of a game that ended this tick -- what SSF_Env.step returned for
+  // that tick (ENV:246-253), before the auto-reset replaces it with the new game's first one; [n_envs][obs_dim] in the batch's
+  // observation dtype, written by auto-resetting step launches for the lanes that finish and for no others; else null.
+  // Behind every older member: none of them moves
+  void* final_obs;
 };
 
 // words of SfKernelArgs::acc behind the SF_EPISODE_STATS_LEN (8) episode statistics

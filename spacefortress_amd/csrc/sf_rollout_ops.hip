@@ -74,6 +74,47 @@ __global__ __launch_bounds__(256) void sf_returns_kernel(int T, int n, const flo
   }
 }
 
+// sf_returns_kernel with the time limit's bootstrap: every episode of this game ends by the clock (Game::isGameOver), so a
+// zero in masks[t+1] marks a truncation, not a terminal state, and the target there is r + gamma * V(last observation) rather
+// than r.  Lane i's reward of such a step is read as rewards[t][i] + gamma * final_value[i] -- float32, one multiply, then one
+// add -- and the recursion is sf_returns_kernel's, operation for operation.  A select, not a blend by (1 - mask): the
+// final_value of an env that never finished is whatever its never-written row gave the critic, and must not be looked at.
+__global__ __launch_bounds__(256) void sf_returns_tl_kernel(int T, int n, const float* rewards, float* value_preds,
+                                                            const float* masks, const float* next_value,
+                                                            const float* final_value, float* returns, int use_gae, float gamma,
+                                                            float gamma_tau) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t N = (size_t)n;
+  const float boot = gamma * final_value[i];
+  if (use_gae) {
+    float v_next = next_value[i];
+    value_preds[(size_t)T * N + i] = v_next;
+    float gae = 0.0f;
+    bool first = true;
+    for (int t = T - 1; t >= 0; t--) {
+      const float m = masks[(size_t)(t + 1) * N + i], v = value_preds[(size_t)t * N + i];
+      float r = rewards[(size_t)t * N + i];
+      r = m == 0.0f ? r + boot : r;
+      const float delta = (r + (gamma * v_next) * m) - v;
+      gae = first ? delta + (gamma_tau * m) * 0.0f : delta + (gamma_tau * m) * gae;
+      first = false;
+      returns[(size_t)t * N + i] = gae + v;
+      v_next = v;
+    }
+  } else {
+    float ret = next_value[i];
+    returns[(size_t)T * N + i] = ret;
+    for (int t = T - 1; t >= 0; t--) {
+      const float m = masks[(size_t)(t + 1) * N + i];
+      float r = rewards[(size_t)t * N + i];
+      r = m == 0.0f ? r + boot : r;
+      ret = ((ret * gamma) * m) + r;
+      returns[(size_t)t * N + i] = ret;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int sf_record_step(int n, const int32_t* reward_dev, const uint8_t* done_dev, float* reward_out, float* mask_out,
@@ -133,6 +174,29 @@ extern "C" int sf_compute_returns(int num_steps, int n, const float* rewards, fl
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     sf_set_error("sf_compute_returns: %s", hipGetErrorString(e));
+    return SF_ERR_HIP;
+  }
+  return SF_OK;
+}
+
+extern "C" int sf_compute_returns_tl(int num_steps, int n, const float* rewards, float* value_preds, const float* masks,
+                                     const float* next_value, const float* final_value, float* returns, int use_gae,
+                                     double gamma, double tau, void* stream) {
+  if (num_steps <= 0 || n <= 0 || !rewards || !masks || !next_value || !returns || (use_gae && !value_preds)) {
+    sf_set_error("sf_compute_returns_tl: bad argument");
+    return SF_ERR_ARG;
+  }
+  if (!final_value) {
+    sf_set_error("sf_compute_returns_tl: final_value is null (float [n]: the critic's value of every env's final observation; "
+                 "sf_compute_returns is the recursion without the time limit's bootstrap)");
+    return SF_ERR_ARG;
+  }
+  // gamma and gamma * tau rounded as in sf_compute_returns
+  hipLaunchKernelGGL(sf_returns_tl_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, num_steps, n, rewards,
+                     value_preds, masks, next_value, final_value, returns, use_gae, (float)gamma, (float)(gamma * tau));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    sf_set_error("sf_compute_returns_tl: %s", hipGetErrorString(e));
     return SF_ERR_HIP;
   }
   return SF_OK;

@@ -51,7 +51,11 @@ def gather_errors(device, clear=False):
 
 
 class FrameRollout(DeviceRollout):
-    def __init__(self, env, num_steps, state_size=1, num_stack=4, layout="time"):
+    def __init__(self, env, num_steps, state_size=1, num_stack=4, layout="time", time_limit_bootstrap=False):
+        if time_limit_bootstrap:
+            raise ValueError("FrameRollout: time_limit_bootstrap is for 1-D observations: image batches have no "
+                             "final-observation output; make the env with auto_reset=False, read the finished envs' frames "
+                             "and restart them with reset_lanes(mask=done)")
         if hasattr(env, "venv"):
             raise ValueError("FrameRollout stores image observations: no SFVecNormalize around the env (rl/train.py:35)")
         if env.obs_type != "image" or not env.default_geometry:

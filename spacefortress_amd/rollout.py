@@ -8,6 +8,14 @@ Here ONE launch per step (`sf_step_record`) writes the next observation straight
 episode / final reward accumulators and `actions[step]`; `compute_returns` is one backward-scan kernel
 (`sf_compute_returns`, bit-identical to the reference's float32 arithmetic).  Tensor names and shapes are
 RolloutStorage's.
+
+time_limit_bootstrap=True: every episode of this game ends by the clock, so a zero in `masks` is a truncation and the
+reference's recursion, which zeroes the value there, is the wrong target.  The rollout then keeps every env's final
+observation (SFVecEnv.enable_final_obs), `final_obs()` hands the rows to the critic, and
+`compute_returns(..., final_value=critic(ro.final_obs()))` adds gamma * V(final observation) to the reward of the step a
+game ended on (`sf_compute_returns_tl`).  One row per env describes one finish: num_steps <= env.max_ticks + 1, the length
+of an episode.  A caller who shortens episodes behind the rollout's back -- set_field("time"), load_lanes -- so that an env
+finishes twice inside one rollout gets the LATER observation's value for both.
 """
 import ctypes as C
 
@@ -21,7 +29,7 @@ def _p(t):
 
 
 class DeviceRollout:
-    def __init__(self, env, num_steps, state_size=1, num_stack=1):
+    def __init__(self, env, num_steps, state_size=1, num_stack=1, time_limit_bootstrap=False):
         # `env`: an SFVecEnv, or an SFVecNormalize around one (the trainer's configuration for 1-D observations,
         # rl/train.py:35-36: observations and rewards reach the storage normalised)
         self.norm = env if hasattr(env, "venv") else None
@@ -30,6 +38,17 @@ class DeviceRollout:
         self._L = _lib.lib()
         T, n, dev = int(num_steps), env.num_envs, env.device
         self.num_steps = T
+        self.time_limit_bootstrap = bool(time_limit_bootstrap)
+        if self.time_limit_bootstrap:
+            if int(num_stack) > 1 or env.is_image:
+                raise ValueError("time_limit_bootstrap is for 1-D observations: a stack of frames has no final-observation "
+                                 "output; make the env with auto_reset=False, read the finished envs' frames and restart "
+                                 "them with reset_lanes(mask=done)")
+            if T > env.max_ticks + 1:
+                raise ValueError("time_limit_bootstrap: num_steps %d > %d, the ticks of an episode: an env would finish twice "
+                                 "in a rollout and one final observation per env cannot describe both" % (T, env.max_ticks + 1))
+            if env.final_obs is None:
+                env.enable_final_obs()
         obs_shape = tuple(env.obs_shape)
         # image observations: obs_shape = (obs_shape[0] * num_stack, ...) as in rl/train.py:38-39; every step stores
         # the whole stack (shifted by one frame, zeroed for finished envs, new frame last)
@@ -160,10 +179,29 @@ class DeviceRollout:
         """num_destruction += sum(info) of rl/train.py:81, from the step kernel's own accumulator (synchronises)."""
         return int(self.env.episode_stats()[3]) - self._kills0
 
-    def compute_returns(self, next_value, use_gae, gamma, tau):
-        """rl/storage.py:50-63 in one launch."""
+    def final_obs(self):
+        """[N, obs_dim]: every env's final observation as the agent sees observations -- through the normaliser when there is
+        one (a copy, statistics as they stand: SFVecNormalize.final_obs), else the env's own rows.  For the critic:
+        compute_returns(..., final_value=critic(ro.final_obs()))."""
+        if not self.time_limit_bootstrap:
+            raise ValueError("final_obs(): this rollout was made without time_limit_bootstrap=True")
+        return self.norm.final_obs() if self.norm is not None else self.env.final_obs
+
+    def compute_returns(self, next_value, use_gae, gamma, tau, final_value=None):
+        """rl/storage.py:50-63 in one launch.  final_value ([N] or [N, 1], the critic's value of final_obs()): the recursion
+        with gamma * final_value added to the reward of every step whose mask is 0 (sfmi.h: sf_compute_returns_tl); required
+        with time_limit_bootstrap=True -- there is no silent fall-back to the recursion that zeroes the value there."""
         n = self.env.num_envs
         nv = next_value.reshape(n).float().contiguous()
+        if final_value is None and self.time_limit_bootstrap:
+            raise ValueError("compute_returns: this rollout was made with time_limit_bootstrap=True: pass "
+                             "final_value=critic(ro.final_obs())")
+        if final_value is not None:
+            fv = final_value.detach().reshape(n).float().contiguous()
+            _lib.check(self._L.sf_compute_returns_tl(self.num_steps, n, _p(self.rewards), _p(self.value_preds), _p(self.masks),
+                                                     _p(nv), _p(fv), _p(self.returns), int(bool(use_gae)), float(gamma),
+                                                     float(tau), self._stream()))
+            return
         _lib.check(self._L.sf_compute_returns(self.num_steps, n, _p(self.rewards), _p(self.value_preds), _p(self.masks),
                                               _p(nv), _p(self.returns), int(bool(use_gae)), float(gamma), float(tau),
                                               self._stream()))

@@ -419,6 +419,7 @@ class SFVecEnv:
         if getattr(self, "_h", None) is not None and self._h:
             self._L.sf_destroy(self._h)
             self._h = None
+        self._final_obs = None
 
     def __del__(self):
         try:
@@ -565,6 +566,36 @@ class SFVecEnv:
         self.events = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device) if on else None
         _lib.check(self._L.sf_set_event_output(self._h, C.c_void_p(self.events.data_ptr()) if on else None))
         return self.events
+
+    def enable_final_obs(self, out=None):
+        """The LAST observation of every game that ends (sfmi.h: sf_set_final_obs_output): from here on every stepping path
+        writes, for each env whose `done` it sets, the row SSF_Env.step returned for that tick -- the one the auto-reset
+        replaces with the new game's first observation -- into a [N, obs_dim] tensor of the env's dtype, and leaves the other
+        rows alone.  What gymnasium calls `final_observation`: every episode here ends by the clock, so the target at `done`
+        bootstraps with V(that row) (DeviceRollout(time_limit_bootstrap=True)).  Allocates a zeroed tensor or adopts `out`,
+        returns it (also `self.final_obs`); enable_final_obs(False) switches it off.  Off by default: with it on the step
+        leaves the split launch (profiles/final_obs.md).  ValueError for image batches and auto_reset=False."""
+        if out is False:
+            _lib.check(self._L.sf_set_final_obs_output(self._h, None))
+            self._final_obs = None
+            return None
+        if self.is_image or self.obs_type == "none":
+            raise ValueError("enable_final_obs: image batches have no final-observation output; make the batch with "
+                             "auto_reset=False, read the finished envs' frames and restart them with reset_lanes(mask=done)")
+        if out is None:
+            out = torch.zeros((self.num_envs, self.obs_dim), dtype=self.obs_dtype, device=self.device)
+        elif not (torch.is_tensor(out) and out.device == self.device and out.dtype == self.obs_dtype and out.is_contiguous()
+                  and tuple(out.shape) == (self.num_envs, self.obs_dim)):
+            raise ValueError("enable_final_obs: out must be a contiguous %s tensor [%d, %d] on %s"
+                             % (self.obs_dtype, self.num_envs, self.obs_dim, self.device))
+        _lib.check(self._L.sf_set_final_obs_output(self._h, C.c_void_p(out.data_ptr())))  # (refuses auto_reset=False, misalignment)
+        self._final_obs = out
+        return out
+
+    @property
+    def final_obs(self):
+        """The tensor enable_final_obs() handed to the library, or None."""
+        return getattr(self, "_final_obs", None)
 
     # ------------------------------------------------------------------ extras
     def check_actions(self):

@@ -117,6 +117,21 @@ class SFVecNormalize:
         self.step_async(actions)
         return self.step_wait()
 
+    def final_obs(self):
+        """The env's final observations (SFVecEnv.enable_final_obs) as the agent would have seen them: a COPY of the rows,
+        normalised with the statistics as they stand at this call -- one frozen sf_normalize launch; no statistic is updated
+        and the env's own rows stay raw.  Rows of envs that have not finished since the buffer was made are as meaningless
+        normalised as they are raw."""
+        raw = self.venv.final_obs
+        if raw is None:
+            raise ValueError("final_obs(): the env's final-observation output is off (SFVecEnv.enable_final_obs)")
+        if not self.ob:
+            return raw.clone()
+        out = torch.empty_like(raw)
+        _lib.check(self._L.sf_normalize(self._h, C.c_void_p(raw.data_ptr()), C.c_void_p(out.data_ptr()), None, None, 1,
+                                        self._stream()))
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.sf_normalizer_destroy(self._h)
