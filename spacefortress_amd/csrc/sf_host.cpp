@@ -273,6 +273,13 @@ void sf_host_fill_consts(const sf_preset& p, double* c) {
   hex_edges(p.big_hex, c + SF_LDS_BIGHEX);
   hex_edges(p.small_hex, c + SF_LDS_SMALLHEX);
   for (int k = 0; k < SF_ATAB_DOUBLES; k++) c[SF_CONST_ATAB + k] = k <= 16 ? atan((double)k / 16.0) : 0.0;
+  // the kernel constants row (a split launch's games' wave reads these as data, sf_lane_dev.h: SfKRow): the very expressions
+  // the other kernels compile in, evaluated by this compiler -- IEEE doubles either way
+  int k = 0;
+#define SF_K(name, value) c[SF_CONST_KROW + k++] = (value);
+  SF_KROW_LIST(SF_K)
+#undef SF_K
+  static_assert(SF_CONST_KROW % 2 == 0 && SF_KROW_DOUBLES % 2 == 0, "the block is staged in 16-byte pieces");
 }
 
 // Everything of baseConfig (SRC/configs.cpp:3-49) but the start velocity is identical in the four presets and is compiled

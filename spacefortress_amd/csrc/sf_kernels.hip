@@ -80,6 +80,8 @@
 // through which the missile pool's entries tell their owner lanes what happened to them; then the observation staging
 #define SF_LDS_EV SF_LDS_DOUBLES
 /* then (sf_step_kernel: kLdsAtab, kLdsStage) behind the BLK event words: atan(k / 16), k = 0..16 (sf_atan2_core), and the staging rows */
+// A split launch stages the WHOLE constants block, [0, SF_LDS_SPLIT_DOUBLES): the cos/sin table, the hexagon edges, the atan
+// table and the kernel constants row in one pass; its event words, hand-over words and staging rows follow that (kLdsEv ...).
 
 // Diagnostic build only (-DSF_STAMPS, tools/stamps.py): shader-clock stamps at phase boundaries,
 // with forced waits so each phase owns its memory latency.  The product build has none of it.
@@ -357,11 +359,21 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   constexpr int NT = SPLIT ? 2 * BLK : BLK;        // threads per workgroup
   static_assert(!SPLIT || (!FUSED && OBSK == 1 && !XTRA), "the split launch exists for the plain step of the default observation");
   static_assert(!FOBS || XTRA, "the final-observation output rides on the XTRA instantiations");
-  constexpr int kTrigPieces = (SF_LDS_DOUBLES / 2 + NT - 1) / NT;
-  // (the LDS map above, for BLK envs; a split launch's hand-over words sit between the atan table and the staging rows:
-  //  the new missiles' (x, y) [BLK d2_t] and meta words [BLK], then four words per tile: fired, pool done | count, stores done)
-  constexpr int kLdsAtab = SF_LDS_DOUBLES + BLK, kLdsHand = kLdsAtab + SF_ATAB_DOUBLES, kLdsHandMeta = kLdsHand + 2 * BLK,
+  // what the workgroup stages into LDS in its one table pass: the cos/sin table; a split launch: the whole constants block --
+  // the hexagon edges, the atan table and the kernel constants row sit right behind the cos/sin table, and 401 pieces of 16
+  // bytes fit the pass that moved 360 (512 threads: one piece each, as before; 256: two; 128: four instead of three plus the
+  // games' wave's atan piece).  The games' wave's own load of the atan table and its LDS write are gone with it.
+  constexpr int kStaged = SPLIT ? SF_LDS_SPLIT_DOUBLES : SF_LDS_DOUBLES;
+  constexpr int kTrigPieces = (kStaged / 2 + NT - 1) / NT;
+  // (the LDS map above, for BLK envs; a split launch's: the staged block with the atan table inside it, the event words, then
+  //  the hand-over words in front of the staging rows: the new missiles' (x, y) [BLK d2_t] and meta words [BLK], then four
+  //  words per tile: fired, pool done | count, stores done.  sf_launch_step's lds_bytes is this map's end.)
+  constexpr int kLdsEv = kStaged;
+  constexpr int kLdsAtab = SPLIT ? SF_CONST_ATAB : kLdsEv + BLK, kLdsHand = SPLIT ? kLdsEv + BLK : kLdsAtab + SF_ATAB_DOUBLES,
+                kLdsHandMeta = kLdsHand + 2 * BLK,
                 kLdsHandFlags = kLdsHandMeta + BLK / 2, kLdsStage = SPLIT ? kLdsHandFlags + BLK / 32 : kLdsHand;
+  static_assert(kLdsEv == SF_LDS_EV || SPLIT, "the other kernels' map is the one above");
+  static_assert(kStaged % 2 == 0 && kLdsAtab % 2 == 0 && kLdsHand % 2 == 0 && kLdsStage % 2 == 0, "16-byte LDS accesses");
   extern __shared__ double lds[];  // [SF_LDS_DOUBLES] cos/sin table, the event words, then the obs staging rows (SF_LDS_*)
   const unsigned tid_all = threadIdx.x;
   const unsigned tid = SPLIT ? (tid_all & (unsigned)(BLK - 1)) : tid_all;  // the env of the workgroup this thread works for
@@ -434,7 +446,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
       d2_t cst0[kTrigPieces];
 #pragma unroll
       for (int k = 0; k < kTrigPieces; k++) {
-        cpi0[k] = min(tid_all + k * NT, (unsigned)(SF_LDS_DOUBLES / 2 - 1));
+        cpi0[k] = min(tid_all + k * NT, (unsigned)(kStaged / 2 - 1));
         cst0[k] = SF_LD(d2_t, (const unsigned char*)consts_p, cpi0[k] * 16u);
       }
       const unsigned m_live = n_word >> SF_MPOOL_SHIFT;
@@ -473,7 +485,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
              kv_mr2 = sfc::missile_hit_r2;
       asm volatile("" : "+v"(kv_speed), "+v"(kv_fx), "+v"(kv_fy), "+v"(kv_w), "+v"(kv_h), "+v"(kv_mr2));
       unsigned wp = 0;
-      unsigned* const evw32 = reinterpret_cast<unsigned*>(lds + SF_LDS_EV) + 2u * (tid & ~63u);
+      unsigned* const evw32 = reinterpret_cast<unsigned*>(lds + kLdsEv) + 2u * (tid & ~63u);
       auto m_row = [&](double x, double y, unsigned meta, d2_t cs, bool valid) __attribute__((always_inline)) {  // (as below)
         const double nx = x + kv_speed * cs.x, ny = y + kv_speed * cs.y;
         const double dx = nx - kv_fx, dy = ny - kv_fy;
@@ -549,8 +561,9 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   Lane L;
   load_lane_early(tb, o, L);  // before the action: its address needs two more kernel arguments and a branch on the action type
   int act_next = load_action(0);
+  // (the atan table: nine pieces of its own; a split launch has it in the block its threads stage below, and no load here)
   const unsigned atab_pi = min(tid, (unsigned)(SF_ATAB_DOUBLES / 2 - 1));
-  const d2_t atab_piece = SF_LD(d2_t, (const unsigned char*)consts_p, (SF_CONST_ATAB / 2 + atab_pi) * 16u);
+  const d2_t atab_piece = SPLIT ? d2_t{0, 0} : SF_LD(d2_t, (const unsigned char*)consts_p, (SF_CONST_ATAB / 2 + atab_pi) * 16u);
   // cos/sin table: 720 doubles = 360 16-byte pieces, six per lane (the last one partial)
   const unsigned char* cb = (const unsigned char*)consts_p;
   // (threads past the end re-load and re-store the last piece: straight-line code, no exec-masked
@@ -559,7 +572,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   unsigned cpi[kTrigPieces];
 #pragma unroll
   for (int k = 0; k < kTrigPieces; k++) {
-    cpi[k] = min(tid_all + k * NT, (unsigned)(SF_LDS_DOUBLES / 2 - 1));
+    cpi[k] = min(tid_all + k * NT, (unsigned)(kStaged / 2 - 1));
     cst[k] = SF_LD(d2_t, cb, cpi[k] * 16u);
   }
   // (behind the last load of the early set: the ten rounds run while those are in flight)
@@ -591,9 +604,9 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   for (int k = 0; k < kTrigPieces; k++) reinterpret_cast<d2_t*>(lds)[cpi[k]] = cst[k];
   // this lane's (hit, out) event words start at zero; the missile pool's entries OR their slot bit into their
   // OWNER's words (wave-private: only lanes of this wave own entries of this tile; LDS is in order per wave)
-  unsigned long long* const evw = reinterpret_cast<unsigned long long*>(lds + SF_LDS_EV) + (tid & ~63u);
+  unsigned long long* const evw = reinterpret_cast<unsigned long long*>(lds + kLdsEv) + (tid & ~63u);
   evw[lane] = 0ull;
-  reinterpret_cast<d2_t*>(lds + kLdsAtab)[atab_pi] = atab_piece;  // (every lane the same nine pieces: no branch)
+  if constexpr (!SPLIT) reinterpret_cast<d2_t*>(lds + kLdsAtab)[atab_pi] = atab_piece;  // (every lane the same nine pieces: no branch)
 
   // ================= round trip 2: live shell slots, predicated by the alive mask ======
   // Slot by slot: a wave ballot skips a slot no lane uses.  The kernel lasts as long as its slowest wave, so
@@ -654,6 +667,14 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   __syncthreads();  // the only workgroup barrier of the kernel
   const double* trig = lds;
   SF_STAMP(3, false);
+  // A split launch's games' wave reads the fp64 constants of its bearings, sector and extras from the staged constants row
+  // as DATA (sf_lane_dev.h: SfKRow): eight broadcast reads here, in front of the key processing and the hand-over's compiler
+  // barrier, back long before the first bearing asks for them.  Compiled in they were some forty scalar moves per tick;
+  // A/B at 65 536 envs against the build that only stages the row: 6.21 -> 6.11 us per launch in loop launches, 6.28 -> 6.19
+  // in graph launches (profiles/step_constants.md; the hexagon edges read the same way measured +0.05 / +0.02 and stay
+  // immediates).  The other instantiations keep the immediates: they have no 32 VGPRs to hold the row in.
+  SfKRow kc;
+  if constexpr (SPLIT) kc = sf_load_krow(lds + SF_CONST_KROW);
 
   // A fused launch unpacks the late set here, once, in front of its tick loop.  One tick per launch unpacks it behind the
   // two bearings (below): unpacked here, the sign extensions of the key timers -- pure ALU on the loaded words -- are
@@ -753,9 +774,10 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   if (L.fl & SF_FL_SHIP_ALIVE) {
     if (AUTOTURN) {
       // stdAngle(ceil(angleTo(ship, fortress)))  (SRC/vector.cpp:42-52)
-      double t = sf_atan2<true>(sfc::fort_y - L.sy, sfc::fort_x - L.sx, lds + kLdsAtab);
+      double t = SPLIT ? sf_atan2_razor(sfc::fort_y - L.sy, sfc::fort_x - L.sx, lds + kLdsAtab, kc)  // (see the bearings below)
+                       : sf_atan2<true>(sfc::fort_y - L.sy, sfc::fort_x - L.sx, lds + kLdsAtab);
       if (t < 0) t += M_PI * 2;
-      double c = ceil(rad2deg(t));  // in [0, 360]
+      double c = ceil(SPLIT ? rad2deg(t, kc) : rad2deg(t));  // in [0, 360]
       int ia = (int)c;
       if (ia >= 360) ia -= 360;  // fmod(360, 360)
       L.angle = ia;
@@ -789,8 +811,11 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   }
 
   // the two bearings the rest of the tick and the observation need, side by side (ILP)
-  double a_pos = sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x, lds + kLdsAtab);
-  double a_vel = sf_atan2_core(L.vy, L.vx, lds + kLdsAtab);
+  // (SPLIT is a constant: one arm of each `SPLIT ? ... : ...` here and below is compiled -- a split launch's takes the
+  //  constants from `kc`, the same operations on the same values)
+  double a_pos = SPLIT ? sf_atan2_razor(L.sy - sfc::fort_y, L.sx - sfc::fort_x, lds + kLdsAtab, kc)
+                       : sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x, lds + kLdsAtab);
+  double a_vel = SPLIT ? sf_atan2_core(L.vy, L.vx, lds + kLdsAtab, kc) : sf_atan2_core(L.vy, L.vx, lds + kLdsAtab);
   if (!FUSED) {
     // the late set's first use, pinned HERE: the timers' words pass through an empty asm together with the two bearings, so
     // nothing that reads them can be scheduled in front of the atan2s, and the set's wait (vmcnt counts only the score chunk
@@ -805,15 +830,16 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   double new_s_vx = 0, new_s_vy = 0;
   bool fort_respawned = false;
   {
-    double ats = rad2deg(a_pos);  // stdAngle: in [-180, 180], only the sign fix applies
-    if (ats < 0) ats += 360;
+    double ats = SPLIT ? rad2deg(a_pos, kc) : rad2deg(a_pos);  // stdAngle: in [-180, 180], only the sign fix applies
+    if (ats < 0) ats += SPLIT ? kc.d360 : 360;
     L.fort_t = will_respawn ? 0 : L.fort_t;  // monitorShipRespawn's mFortress.mTimer = 0 (SRC/game.cpp:155)
     fort_respawned = !(L.fl & SF_FL_FORT_ALIVE) && L.fort_death_t > sfc::fort_respawn;
     L.fort_t = fort_respawned ? 0 : L.fort_t;
     L.fl |= fort_respawned ? SF_FL_FORT_ALIVE : 0u;
     const bool ship_up = L.fl & SF_FL_SHIP_ALIVE;
     {
-      double q = ceil(SF_DIV(ats, sfc::sector_size)) * sfc::sector_size;  // in [0, 360]
+      double q = SPLIT ? ceil(sf_div_const(ats, kc.d10, kc.inv10)) * kc.d10  // (SF_DIV's form)
+                       : ceil(SF_DIV(ats, sfc::sector_size)) * sfc::sector_size;  // in [0, 360]
       int fa = (int)q;
       fa -= fa >= 360 ? 360 : 0;
       L.fort_angle = ship_up ? fa : L.fort_angle;
@@ -1266,7 +1292,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   if constexpr (OBSK == 1) {  // the host guarantees: features, float32, n_envs % 64 == 0, aligned output (sf_launch_step)
     constexpr int DIM = AUTOTURN ? 17 : 19;
     float* stage = reinterpret_cast<float*>(lds + kLdsStage);
-    const Extras e = compute_extras(a, L, a_pos, a_vel);
+    const Extras e = SPLIT ? compute_extras(a, L, a_pos, a_vel, kc) : compute_extras(a, L, a_pos, a_vel);
     write_features_f32<DIM>(stage + tid * DIM, L, e, a.real_shell_count);
     if ((i & ~63u) < (unsigned)n_envs_p)  // the padding waves behind the batch write nothing
       flush_features_f32<DIM>(stage + (tid & ~63u) * DIM, (float*)obs + (so + (i & ~63u)) * DIM, lane);
@@ -1357,8 +1383,10 @@ hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, con
     said = true;
   }
   const unsigned grid = (unsigned)(a.lanes / blk);
+  // (sf_step_kernel's LDS map: the cos/sin table, the event words, the atan table -- a split launch: the staged constants
+  //  block, the event words, the hand-over words -- then the observation staging rows)
   size_t lds_bytes = (size_t)(SF_LDS_DOUBLES + blk + SF_ATAB_DOUBLES) * sizeof(double) + (size_t)blk * a.obs_dim * elem;
-  if (split) lds_bytes += (size_t)(2 * blk + blk / 2 + blk / 32) * sizeof(double);
+  if (split) lds_bytes = (size_t)(SF_LDS_SPLIT_DOUBLES + blk + 2 * blk + blk / 2 + blk / 32) * sizeof(double) + (size_t)blk * a.obs_dim * elem;
 #define SF_GO2(AT, SH, FU, OK, XT, BL, FO)                                                                            \
   hipLaunchKernelGGL((sf_step_kernel<AT, SH, FU, OK, XT, BL, FO>), dim3(grid), dim3((BL) > 1000 ? 2 * ((BL) - 1000) : (BL)), lds_bytes, stream, a.state,    \
                      a.consts, actions, a.n_envs, act_type, reward, done, info, a, obs, vec_ok, n_steps)

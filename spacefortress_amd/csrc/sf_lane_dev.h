@@ -397,6 +397,115 @@ __device__ __forceinline__ Extras compute_extras(const SfKernelArgs& a, const La
   return e;
 }
 
+// ---- the same bearings, sector arithmetic and extras with their fp64 constants as DATA (a split launch's games' wave) ----
+// The instruction set has no 64-bit literals: a double compiled in is a pair of scalar moves, and with every SGPR in use the
+// compiler builds the pair again in front of each use.  A wave alone on its SIMD pays an issue turn for each of them --
+// some 40 per tick in the two atan2s, rad2deg, the sector and computeExtra.  SfKRow holds those constants in VGPRs, filled
+// by eight broadcast LDS reads from the constants row the workgroup staged (sf_layout.h: SF_KROW_LIST, written by
+// sf_host_fill_consts from the same expressions); measured at 65 536 envs: -0.10 us per launch (profiles/step_constants.md).
+// The functions below restate rad2deg, sf_atan2_core, sf_atan2 and compute_extras operation for operation, in the same
+// order, on the same values -- with -ffp-contract=off the same bits (tests/test_gpu_step_constants.py plays both for 300
+// ticks and compares every bit).  They are separate functions, not a template over the originals: the kernels that keep
+// the immediates (no registers to spare: 176 VGPRs at two waves per SIMD) must stay what they were instruction for
+// instruction, and with the originals written over a constants type six of them came out of the compiler with other registers.
+struct SfKRow {
+#define SF_K(name, value) double name;
+  SF_KROW_LIST(SF_K)
+#undef SF_K
+};
+static_assert(sizeof(SfKRow) == SF_KROW_DOUBLES * sizeof(double) && SF_CONST_KROW % 2 == 0 && SF_KROW_DOUBLES % 2 == 0, "SF_KROW_LIST");
+namespace sfkrow {  // the row's values against what the originals compile in
+#define SF_K(name, value) constexpr double name = (value);
+SF_KROW_LIST(SF_K)
+#undef SF_K
+static_assert(pi == M_PI && half_pi == 1.5707963267948966 && inv_pi == 1.0 / (double)(M_PI) && d10 == (double)sfc::sector_size &&
+              inv10 == 1.0 / (double)sfc::sector_size && ndist_a == sfc::ndist_a && ndist_b == sfc::ndist_b &&
+              inv_ndist_b == 1.0 / (double)sfc::ndist_b, "SF_KROW_LIST");
+}  // namespace sfkrow
+__device__ __forceinline__ SfKRow sf_load_krow(const double* row) {  // `row`: 16-byte aligned, in LDS, the same for every lane
+  d2_t v[SF_KROW_DOUBLES / 2];
+#pragma unroll
+  for (int k = 0; k < SF_KROW_DOUBLES / 2; k++) v[k] = reinterpret_cast<const d2_t*>(row)[k];
+  SfKRow K;
+  int k = 0;
+#define SF_K(name, value) K.name = (k & 1) ? v[k / 2].y : v[k / 2].x; k++;
+  SF_KROW_LIST(SF_K)
+#undef SF_K
+  return K;
+}
+__device__ __forceinline__ double rad2deg(double a, const SfKRow& kc) { return sf_div_const(a, kc.pi, kc.inv_pi) * kc.d180; }
+__device__ __forceinline__ double sf_atan2_core(double y, double x, const double* atab, const SfKRow& kc) {
+  const double ax = fabs(x), ay = fabs(y);
+  const double u = __builtin_fmax(ax, ay), v = __builtin_fmin(ax, ay);
+  const double ru = sf_recip(u);
+  double q = v * ru;
+  q = __builtin_fma(__builtin_fma(-u, q, v), ru, q);
+  const double k = rint(q * kc.d16), c = k * kc.inv16;
+  const double den = __builtin_fma(q, c, 1.0), num = q - c;
+  const double rd = sf_recip(den);
+  double t = num * rd;
+  t = __builtin_fma(__builtin_fma(-den, t, num), rd, t);
+  const double s = t * t;
+  double p = __builtin_fma(s, kc.c9, kc.c7);
+  p = __builtin_fma(s, p, kc.c5);
+  p = __builtin_fma(s, p, kc.c3);
+  double a = atab[(int)k] + __builtin_fma(t, p * s, t);
+  a = ay > ax ? kc.half_pi - a : a;
+  a = x < 0 ? kc.pi - a : a;
+  return copysign(a, y);
+}
+__device__ __forceinline__ double sf_atan2_razor(double y, double x, const double* atab, const SfKRow& kc) {  // sf_atan2<true>
+  double r = sf_atan2_core(y, x, atab, kc);
+  const double ax = fabs(x), ay = fabs(y);
+  const bool ny = ax * 0x1p27 < ay;
+  const bool nx = (x < 0) & (ay * 0x1p27 < ax);
+  if (__ballot(ny | nx) != 0ull) {
+    if (ny | nx) {
+      const double t = ny ? x / y : y / x;
+      const double hi = ny ? 1.5707963267948966 : 3.141592653589793;
+      const double lo = ny ? 6.123233995736766e-17 : 1.2246467991473532e-16;
+      r = copysign(hi, y) + (ny ? copysign(lo, y) - t : copysign(lo, y) + t);
+    }
+  }
+  const double deg = sf_div_const(fabs(r), kc.pi, kc.inv_pi) * kc.d180, kd = rint(deg);
+  const bool rz = !(ny | nx) & (fabs(deg - kd) < 1e-9) & (y != 0.0);
+  if (__ballot(rz) != 0ull) {
+    if (rz) {
+      const double* e = kDegDD[(int)kd];
+      const double ph = e[0], pl = e[1], ch = e[2], cl = e[3], sh = e[4], sl = e[5];
+      const double p1 = ay * ch, e1 = __builtin_fma(ay, ch, -p1);
+      const double p2 = x * sh, e2 = __builtin_fma(x, sh, -p2);
+      const double d = p1 - p2;
+      const double bb = d - p1, err = (p1 - (d - bb)) + (-p2 - bb);
+      const double lo = err + (e1 - e2) + (ay * cl - x * sl);
+      const double N = d + lo, D = x * ch + ay * sh;
+      r = copysign(ph + (pl + N / D), y);
+    }
+  }
+  return r;
+}
+__device__ __forceinline__ Extras compute_extras(const SfKernelArgs& a, const Lane& L, double a_pos, double a_vel, const SfKRow& kc) {
+  Extras e;
+  double o = rad2deg(a_pos, kc) - (double)L.angle + kc.d180;
+  if (o < -kc.d180) o = o + kc.d360;
+  e.aim = o;
+  {
+    const double dy = L.sy - sfc::fort_y;
+    double ov;
+    if (dy == 0)
+      ov = sf_atan2<false>(-(sfc::fort_y - L.sy), sfc::fort_x - L.sx);
+    else
+      ov = dy < 0 ? (-kc.pi - a_pos) : (kc.pi - a_pos);
+    double diff = a_vel - ov;
+    if (diff > kc.pi) diff -= M_PI * 2;
+    if (diff < -kc.pi) diff += M_PI * 2;
+    e.vdir = (L.vx * L.vx + L.vy * L.vy == 0.0) ? 0.0 : rad2deg(diff, kc);
+  }
+  const double fdist = fabs(L.sx - sfc::fort_x);
+  e.ndist = -1 + sf_div_const(fdist - kc.ndist_a, kc.ndist_b, kc.inv_ndist_b);
+  return e;
+}
+
 // One observation row (ENV:95-157) written to `o` (an LDS staging row or global memory).
 template <typename T>
 __device__ __forceinline__ void write_obs(const SfKernelArgs& a, T* o, const Lane& L, const Extras& e) {

@@ -236,10 +236,24 @@ constexpr FieldMeta kFields[SF_F_COUNT] = {
 #define SF_LDS_TRIG 0
 #define SF_LDS_BIGHEX 720
 #define SF_LDS_SMALLHEX 744
-#define SF_CONST_ATAB 768 /* atan(k / 16), k = 0..16 (+ one pad): the table of the kernel's atan2 (sf_atan2_core) */
+//   [768, 786)  atan(k / 16), k = 0..16 (+ one pad): the table of the kernels' atan2 (sf_atan2_core)
+//   [786, 802)  the kernel constants row (SF_KROW_LIST): the fp64 constants of the two bearings, the fortress sector and
+//               computeExtra, which the games' wave of a split launch reads from LDS as data instead of building each of
+//               them from two scalar moves in front of every use (sf_lane_dev.h: SfKRow; profiles/step_constants.md)
+// A split launch stages the whole block into LDS in its one table pass (SF_LDS_SPLIT_DOUBLES), the other kernels the
+// cos/sin table (SF_LDS_DOUBLES).
+#define SF_CONST_ATAB 768
 #define SF_ATAB_DOUBLES 18
-#define SF_CONST_DOUBLES (SF_CONST_ATAB + SF_ATAB_DOUBLES)
+#define SF_CONST_KROW (SF_CONST_ATAB + SF_ATAB_DOUBLES)
+// K(name, the expression the kernels compile in): sf_host_fill_consts evaluates the same expressions into the row, in this order
+#define SF_KROW_LIST(K)                                                                                                 \
+  K(pi, 3.14159265358979323846) K(half_pi, 1.5707963267948966) K(inv_pi, 1.0 / 3.14159265358979323846) K(d180, 180.0)  \
+  K(d360, 360.0) K(c9, 1.0 / 9.0) K(c7, -1.0 / 7.0) K(c5, 0.2) K(c3, -1.0 / 3.0) K(inv16, 0.0625) K(d10, 10.0)          \
+  K(inv10, 1.0 / 10.0) K(ndist_a, 40.0) K(ndist_b, 80.0) K(d16, 16.0) K(inv_ndist_b, 1.0 / 80.0)
+#define SF_KROW_DOUBLES 16
+#define SF_CONST_DOUBLES (SF_CONST_KROW + SF_KROW_DOUBLES)
 #define SF_LDS_DOUBLES 720 /* what a workgroup stages into LDS: the cos/sin table (indexed per lane) */
+#define SF_LDS_SPLIT_DOUBLES SF_CONST_DOUBLES /* ... and a split launch's: the whole constants block, in the same pass */
 
 // The 12 hexagon edges as Hexagon::isInside forms them (SRC/hexagon.cpp:38-42), X(nx, ny, px, py),
 // for radius 200 / 40 (bigHex / smallHex of every preset, SRC/configs.cpp:34-35).  Compiled into the
