@@ -20,6 +20,11 @@ each env's final observation and the returns bootstrap with the critic's value o
 per update (DeviceRollout(time_limit_bootstrap=True), INTEGRATION.md "Episodes end by the clock").
 
     python examples/ppo_loop.py --time-limit-bootstrap --envs 256 --steps 16 --iters 2
+
+--frame-skip K: every action is played for K ticks by one launch (SFVecEnv(frame_skip=K), include/sfmi_repeat.h); rewards are
+summed over the window, an env that finishes inside it stops there, an image batch draws one frame per action.  Default 1.
+
+    python examples/ppo_loop.py --obs image --frame-skip 4 --envs 1024 --steps 32 --iters 5
 """
 import argparse
 import os
@@ -71,7 +76,7 @@ class ConvActorCritic(nn.Module):
 
 def main_image(a):
     """The image path: FrameRollout instead of DeviceRollout(env, T, num_stack=4); no `observations` tensor anywhere."""
-    env = SFVecEnv(a.envs, gametype=a.gametype, obs_type="image", spawn_stride=1)
+    env = SFVecEnv(a.envs, gametype=a.gametype, obs_type="image", spawn_stride=1, frame_skip=a.frame_skip)
     ro = FrameRollout(env, a.steps, num_stack=4)
     net = ConvActorCritic(4, env.n_actions).to(env.device)
     opt = torch.optim.Adam(net.parameters(), lr=7e-4)
@@ -121,13 +126,15 @@ def main():
     ap.add_argument("--mini-batches", type=int, default=4)
     ap.add_argument("--time-limit-bootstrap", action="store_true",
                     help="features: bootstrap the returns at an episode's end with V(final observation) instead of 0")
+    ap.add_argument("--frame-skip", type=int, default=1, metavar="K",
+                    help="ticks every action is played for, in one launch (1: a tick per step)")
     a = ap.parse_args()
     torch.manual_seed(0)
     if a.obs == "image":
         if a.time_limit_bootstrap:
             ap.error("--time-limit-bootstrap is for --obs features (image batches have no final-observation output)")
         return main_image(a)
-    envs = SFVecNormalize(SFVecEnv(a.envs, gametype=a.gametype, spawn_stride=1))
+    envs = SFVecNormalize(SFVecEnv(a.envs, gametype=a.gametype, spawn_stride=1, frame_skip=a.frame_skip))
     log = envs.venv.enable_episode_log()
     ro = DeviceRollout(envs, a.steps, time_limit_bootstrap=a.time_limit_bootstrap)
     net = ActorCritic(envs.venv.obs_dim, envs.venv.n_actions).to(envs.device)

@@ -179,6 +179,11 @@ MASKED_SYMBOLS = {
     "sf_eplog_restart_where": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# every symbol include/sfmi_repeat.h declares (action repeat): bound like SYMBOLS
+REPEAT_SYMBOLS = {
+    "sf_step_repeat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
+}
+
 # what the wrappers answer to `.reset_lanes`: their per-env memory would go stale behind a masked reset
 NO_RESET_LANES = ("%s has no reset_lanes(): its per-env memory (frame stacks, return accumulators, start flags, masks) has no "
                   "rule for a masked reset yet.  Call SFVecEnv.reset_lanes on the bare env and rebuild the wrapper's state, or "
@@ -196,7 +201,7 @@ def lib():
                 "libsfmi.so is missing (%s): build it with `python -m spacefortress_amd.build` "
                 "(there is no CPU fallback)" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(MASKED_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(MASKED_SYMBOLS.items()) + list(REPEAT_SYMBOLS.items()):
             if not hasattr(L, name) and os.environ.get("SFMI_LIB_PATH"):
                 continue  # an older diagnostic build (A/B against an earlier round's library): entry points added since
             f = getattr(L, name)

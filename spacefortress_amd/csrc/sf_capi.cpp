@@ -350,6 +350,41 @@ extern "C" int sf_step(sf_batch* b, const void* actions_dev, int act_type, void*
   return launch_steps(b, d, obs_dev, stream);
 }
 
+// sfmi_repeat.h.  One REPEAT launch of the step kernel; an image batch's frames: one sfb_render from the draw records it left.
+extern "C" int sf_step_repeat(sf_batch* b, const void* actions_dev, int act_type, int repeat, void* obs_dev, int32_t* reward_dev,
+                              uint8_t* done_dev, uint8_t* info_dev, uint8_t* ticks_dev, void* stream) {
+  if (!b || !actions_dev) {
+    sf_set_error("sf_step_repeat: null batch or actions");
+    return SF_ERR_ARG;
+  }
+  if (check_act_type("sf_step_repeat", act_type) != SF_OK) return SF_ERR_ARG;
+  if (repeat < 1 || repeat > 255) {
+    sf_set_error("sf_step_repeat: repeat must be in [1, 255] (got %d)", repeat);
+    return SF_ERR_ARG;
+  }
+  if (!b->args.auto_reset) {
+    sf_set_error("sf_step_repeat: a SF_FLAG_NO_AUTO_RESET batch has no action repeat: an env that finishes inside the window "
+                 "would have to be frozen in place, and a parked lane is given its new game; step such a batch tick by tick");
+    return SF_ERR_ARG;
+  }
+  if (repeat == 1) {  // sf_step itself; every env plays its one tick
+    StepLaunch d{"sf_step_repeat", actions_dev, act_type, 1, false, reward_dev, done_dev, info_dev};
+    const int rc = launch_steps(b, d, obs_dev, stream);
+    if (rc != SF_OK) return rc;
+    DeviceGuard guard(b->device);
+    if (ticks_dev) HIP_TRY(hipMemsetAsync(ticks_dev, 1, (size_t)b->n_envs, (hipStream_t)stream));
+    return SF_OK;
+  }
+  DeviceGuard guard(b->device);
+  const bool image = sfb_is_image(b);
+  SF_FLUSH_VIEW(b, stream);
+  HIP_TRY(sf_launch_step_repeat(b->args, b->autoturn, b->preset.shaped != 0, actions_dev, act_type, image ? nullptr : obs_dev,
+                                reward_dev, done_dev, info_dev, ticks_dev, repeat, (hipStream_t)stream));
+  b->draw_current = b->args.draw != nullptr;  // (an image batch's launch leaves the draw records of the state the window ends in)
+  if (image && obs_dev) return sfb_render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
+  return SF_OK;
+}
+
 int sf_step_with_norm_partials(sf_batch* b, const void* actions_dev, int act_type, void* obs_dev, int32_t* reward_dev,
                                uint8_t* done_dev, uint8_t* info_dev, double* partials, double* ret, double gamma, int* rows_out,
                                void* stream) {

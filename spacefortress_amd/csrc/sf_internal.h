@@ -7,12 +7,16 @@
 #include "sf_layout.h"
 #include "sfmi.h"
 #include "sfmi_masked.h"
+#include "sfmi_repeat.h"
 
 // sf_kernels.hip: the hot path
 hipError_t sf_launch_reset(const SfKernelArgs& a, int first, unsigned cursor0, unsigned stride, void* obs,
                            hipStream_t stream);
 hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, const void* actions, int act_type, void* obs,
                           int32_t* reward, uint8_t* done, uint8_t* info, int n_steps, bool fused, hipStream_t stream);
+// `repeat` ticks of one action per env, one row of outputs (sfmi_repeat.h: sf_step_repeat); ticks: uint8 [n_envs] or null
+hipError_t sf_launch_step_repeat(const SfKernelArgs& a, bool autoturn, bool shaped, const void* actions, int act_type, void* obs,
+                                 int32_t* reward, uint8_t* done, uint8_t* info, uint8_t* ticks, int repeat, hipStream_t stream);
 
 // sf_state_ops.hip: the state tools
 // env.reset() in the envs whose byte of mask [n_envs] is not zero (sfmi.h: sf_reset_lanes); obs may be null

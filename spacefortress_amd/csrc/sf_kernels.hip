@@ -102,6 +102,88 @@
 #define SF_SIN(ang) trig[2 * (ang) + 1]
 #define SF_ST(T, base, off, v) sf_store<T>(reinterpret_cast<T*>((base) + (off)), (T)(v))
 
+// ---- three pieces of sf_step_kernel's tick that a REPEAT launch runs once, behind its tick loop: macros over the kernel's own
+//      names, so that the tick of every other instantiation is the text it was (as always_inline lambdas in front of the loop
+//      they gave all 108 other instantiations other instructions; as macros none: profiles/frame_skip.md)
+// A lane that started a new game while others of its tile play on (only possible when episodes are out of step:
+// sf_set_field, a reset of part of a tile; a REPEAT launch: the lanes parked in the window) must take its entries out of the
+// shared pool: DN = the ballot of those lanes.  With every lane of the tile done in the same tick -- the regular case -- the
+// pool is simply emptied.  (a split launch first waits for the missile wave's acknowledgement of this tick's rows)
+#define SF_PURGE_POOL(DN) \
+  { \
+    const unsigned long long dn_ = (DN); \
+    if (dn_ != 0ull) { \
+      if (dn_ == ~0ull) { \
+        L.mpool = 0; \
+      } else { \
+        const unsigned n_before = (unsigned)__builtin_amdgcn_readfirstlane((int)L.mpool); \
+        unsigned wp = 0; \
+        if constexpr (SPLIT) { \
+          unsigned spins = 0u; \
+          while (__builtin_amdgcn_readfirstlane((int)hflags[2]) == 0 && ++spins < kSpinLimit) __builtin_amdgcn_s_sleep(1); \
+          if (spins >= kSpinLimit && lane == 0u) atomicAdd(&a.acc[SF_ACC_HANDOVER], 1ull); \
+          asm volatile("" ::: "memory"); \
+        } \
+_Pragma("unroll 1") \
+        for (unsigned r = 0; 64u * r < n_before; r++) { \
+          const u4_t pr = __builtin_amdgcn_raw_buffer_load_b128(rs, o.o16 + r * 1024u, SF_GOFF(missile_pos, 0), 16); \
+          const unsigned pm = __builtin_amdgcn_raw_buffer_load_b32(rs, o.o4 + r * 256u, SF_GOFF(missile_meta, 0), 16); \
+          const bool keep = (64u * r + lane < n_before) && !((dn_ >> SF_MM_OWNER(pm)) & 1ull); \
+          const unsigned long long kb = __ballot(keep); \
+          const unsigned idx = wp + __builtin_amdgcn_mbcnt_hi((unsigned)(kb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kb, 0u)); \
+          wp += (unsigned)__popcll(kb); \
+          sf_buf_st128<kStAux>(pr, rs, keep ? idx * 16u : SF_OOB, SF_GOFF(missile_pos, 0)); \
+          __builtin_amdgcn_raw_buffer_store_b32(pm, rs, keep ? idx * 4u : SF_OOB, SF_GOFF(missile_meta, 0), kStAux); \
+        } \
+        L.mpool = wp; \
+      } \
+    } \
+  }
+// the env's draw record (sf_drawrec.h) -- header, ship, fortress; the missiles' entries go out as the pool is walked.
+// NEWGAME: the env starts a new game here (it has no projectiles); PROJ: sfd::hud_flags_near of its projectiles
+#define SF_DRAW_HEADER(NEWGAME, PROJ) \
+  { \
+    typedef float f4_t __attribute__((ext_vector_type(4))); \
+    const sfd::Header h = sfd::make_header(L.sx, L.sy, L.angle, (L.fl & SF_FL_SHIP_ALIVE) != 0u, (L.fl & SF_FL_FORT_ALIVE) != 0u, L.fort_angle, \
+                                           L.points, L.vlner, L.fort_vuln_t, L.mmask, L.smask, \
+                                           (NEWGAME) ? 0u : (PROJ) /* a new game has no projectiles */, a.draw_pics != 0, L.time); \
+    const __amdgpu_buffer_rsrc_t rs_dr = __builtin_amdgcn_make_buffer_rsrc( \
+        a.draw + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * (size_t)SF_DR_TILE_BYTES, 0, SF_DR_TILE_BYTES, 0x00020000); \
+    const unsigned d0 = real ? lane * (unsigned)SF_DR_LANE_STRIDE : SF_OOB; \
+    sf_buf_st128<0>(u4_t{h.w[0], h.w[1], h.w[2], h.w[3]}, rs_dr, d0, 0); \
+    sf_buf_st128<0>(u4_t{h.w[4], h.w[5], h.w[6], h.w[7]}, rs_dr, d0, SF_DR_PIECE_STRIDE); \
+    sf_buf_st128<0>(__builtin_bit_cast(u4_t, (d2_t{L.sx, L.sy})), rs_dr, d0, (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_SHIP) * SF_DR_PIECE_STRIDE); \
+  }
+// the lane's observation row, by way of the wave's staging rows, into row ROW (in units of n_envs rows) of the output; BPOS,
+// BVEL: the two bearings of the state.  OBSK == 1: the host guarantees features, float32, n_envs % 64 == 0, an aligned output
+// (sf_launch_step); the padding waves behind the batch write nothing.  NEWGAME && a.ref_reset_obs: a new game's observation
+// as the reference returns it (sf_launch_step keeps such batches out of OBSK == 1)
+#define SF_WRITE_OBSERVATION(ROW, BPOS, BVEL, NEWGAME) \
+  { \
+    if constexpr (OBSK == 1) { \
+      constexpr int DIM = AUTOTURN ? 17 : 19; \
+      float* stage = reinterpret_cast<float*>(lds + kLdsStage); \
+      const Extras e = SPLIT ? compute_extras(a, L, BPOS, BVEL, kc) : compute_extras(a, L, BPOS, BVEL); \
+      write_features_f32<DIM>(stage + tid * DIM, L, e, a.real_shell_count); \
+      if ((i & ~63u) < (unsigned)n_envs_p) \
+        flush_features_f32<DIM>(stage + (tid & ~63u) * DIM, (float*)obs + (ROW + (i & ~63u)) * DIM, lane); \
+    } else if (obs != nullptr && a.obs_type != 3) { \
+      Extras e = compute_extras(a, L, BPOS, BVEL); \
+      if (a.ref_reset_obs && NEWGAME) e = Extras{0.0, 0.0, 0.0}; \
+      if (a.obs_f64) { \
+        double* stage = lds + kLdsStage; \
+        write_obs<double>(a, stage + tid * a.obs_dim, L, e); \
+        flush_obs_wave<double>(a, stage + (tid & ~63u) * a.obs_dim, (double*)obs + ROW * a.obs_dim, i & ~63u, lane, \
+                               obs_vec_ok); \
+      } else { \
+        float* stage = reinterpret_cast<float*>(lds + kLdsStage); \
+        write_obs<float>(a, stage + tid * a.obs_dim, L, e); \
+        flush_obs_wave<float>(a, stage + (tid & ~63u) * a.obs_dim, (float*)obs + ROW * a.obs_dim, i & ~63u, lane, \
+                              obs_vec_ok); \
+      } \
+    } \
+  }
+
 namespace {
 
 // What one tick adds to the statistics (SRC/game.hh:29-43); flushed with atomics.
@@ -343,8 +425,13 @@ __global__ __launch_bounds__(SF_BLOCK) void sf_reset_kernel(SfKernelArgs a, int 
 // BLKP = 1000 + BLK is a SPLIT launch: BLK envs per workgroup and a second wave per tile that moves the tile's missile pool
 // while the first plays the 64 games (see "the tile's MISSILE wave" below); what sf_launch_step takes for the plain step of the
 // default observation of batches up to 65 536 envs (beyond, a SIMD has several games' waves to interleave anyway).
+// BLKP = 2000 + BLK is a REPEAT launch (sf_step_repeat: action repeat, frame skip): the fused tick loop on ONE action per env,
+// one row of outputs behind it, an env whose game ends inside the window parked for the rest of it (see "a REPEAT launch" in
+// front of the tick loop).  It rides on FUSED = XTRA = true at BLK 256 and tests a.final_obs at run time: AUTOTURN x SHAPED x
+// OBSK instantiations of their own, spelled in BLKP and not as one more template flag so that every other instantiation keeps
+// its symbol as well as its instructions (profiles/frame_skip.md).
 template <bool AUTOTURN, bool SHAPED, bool FUSED, int OBSK, bool XTRA, int BLKP, bool FOBS = false>
-__global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_step_kernel(unsigned char* state_p, const double* consts_p,
+__global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP)) void sf_step_kernel(unsigned char* state_p, const double* consts_p,
                                                           const void* actions, int n_envs_p, int act_type,
                                                           int32_t* reward_out, uint8_t* done_out, uint8_t* info_out,
                                                           SfKernelArgs a, void* obs, int obs_vec_ok, int n_steps) {
@@ -354,11 +441,14 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   // segment first (on a firmware without the feature the compiler's compatibility preamble loads them).  The
   // three output pointers ride along: the epilogue then stores without a scalar load and its wait.
   // BLKP = 1000 + BLK: a SPLIT launch -- BLK envs per workgroup and as many threads again, the tiles' MISSILE waves (below)
-  constexpr bool SPLIT = BLKP > 1000;
-  constexpr int BLK = SPLIT ? BLKP - 1000 : BLKP;  // envs per workgroup
+  // BLKP = 2000 + BLK: a REPEAT launch (sf_step_repeat) -- n_steps ticks of ONE action per env, one row of outputs (below)
+  constexpr bool REPEAT = BLKP > 2000;
+  constexpr bool SPLIT = BLKP > 1000 && !REPEAT;
+  constexpr int BLK = REPEAT ? BLKP - 2000 : (SPLIT ? BLKP - 1000 : BLKP);  // envs per workgroup
   constexpr int NT = SPLIT ? 2 * BLK : BLK;        // threads per workgroup
   static_assert(!SPLIT || (!FUSED && OBSK == 1 && !XTRA), "the split launch exists for the plain step of the default observation");
   static_assert(!FOBS || XTRA, "the final-observation output rides on the XTRA instantiations");
+  static_assert(!REPEAT || (FUSED && XTRA && !FOBS && BLK == SF_BLOCK), "the action repeat rides on the fused XTRA instantiations (a.final_obs: a run-time test)");
   // what the workgroup stages into LDS in its one table pass: the cos/sin table; a split launch: the whole constants block --
   // the hexagon edges, the atan table and the kernel constants row sit right behind the cos/sin table, and 401 pieces of 16
   // bytes fit the pass that moved 360 (512 threads: one piece each, as before; 256: two; 128: four instead of three plus the
@@ -682,10 +772,22 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   // some eighty instructions after its issue) stands in front of the ship and both atan2s instead of under them.
   if (FUSED) unpack_lane_late(late, L);
   const int n_iter = FUSED ? n_steps : 1;
+  // ---- a REPEAT launch (sf_step_repeat, sfmi_repeat.h): the n_steps ticks play ONE action per env and leave ONE row of outputs
+  //      -- the summed reward, done, the OR of the ticks' info, events and render hints, the ticks played -- and the
+  //      observation and draw record of the state the window ends in.  An env whose game ends inside the window is PARKED:
+  //      the tick is straight-line code with wave-wide ballots and a pool the tile shares, so the lane ticks on, but as a game
+  //      in which nothing can happen (ship dead and not due back within 255 ticks, no projectiles: no shot, no shell, no
+  //      respawn, no event -- the spawn cursor and prev_vlner, which is all new_game reads, stay what the finishing tick left)
+  //      and with every output masked; behind the loop it gets its new game, of which no tick has been played.
+  //      rp_w: ticks played (bits 0..7), info (8), render hint (9), parked (10)
+  constexpr unsigned kRpInfo = 1u << 8, kRpDied = 1u << 9, kRpParked = 1u << 10;
+  unsigned rp_w = 0u, rp_events = 0u, rp_proj = 0u;
+  int rp_reward = 0;
+  double rp_apos = 0, rp_avel = 0;  // the last tick's bearings, for the observation behind the loop
   for (int step = 0; step < n_iter; step++) {
   int act = (XTRA && act_type == SF_ACT_SAMPLED) ? act_sampled : act_next;
   if (FUSED) {
-    if (step + 1 < n_iter) {
+    if (!REPEAT && step + 1 < n_iter) {
       act_next = load_action(step + 1);  // in flight while this tick computes
       if (XTRA && act_type == SF_ACT_SAMPLED) act_sampled = sample_action(step + 1);
     }
@@ -697,7 +799,8 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
       load_spawn();
     }
   }
-  const size_t so = (size_t)step * (size_t)a.n_envs;  // this tick's row of the output arrays
+  const size_t so = REPEAT ? (size_t)0 : (size_t)step * (size_t)a.n_envs;  // this tick's row of the output arrays
+  const bool rp_parked = REPEAT && (rp_w & kRpParked) != 0u;  // parked by an earlier tick of this window
   // image batches: this tick leaves the envs' draw records for the frame kernel (sf_drawrec.h) -- of a fused launch, the
   // last tick does.  `dr_proj`: where this env's projectiles come near the score / the bar (sfd::hud_flags_near)
   const bool draw_now = OBSK != 1 && a.draw != nullptr && (!FUSED || step + 1 == n_iter);  // uniform
@@ -705,7 +808,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
 
   const int act_raw = act;  // what rollouts.actions[step] records
   if (act < 0 || act >= a.n_actions) {
-    atomicAdd(&a.acc[SF_ACC_BAD_ACTION], 1ull);  // reference: IndexError; here NOOP + counted (sf_check_actions)
+    if (!rp_parked) atomicAdd(&a.acc[SF_ACC_BAD_ACTION], 1ull);  // reference: IndexError; here NOOP + counted (sf_check_actions)
     act = 0;
   }
   const unsigned keys = (unsigned)(a.action_keys >> (4 * act)) & 0xFu;
@@ -1176,7 +1279,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
   L.c_small += (unsigned)S.small_hex_deaths;
   L.c_shell += (unsigned)S.shell_deaths;
   L.c_destroyed += (unsigned)S.destroyed;
-  if (XTRA && !a.auto_reset) {  // uniform
+  if (XTRA && !REPEAT && !a.auto_reset) {  // uniform (a REPEAT launch: auto-resetting batches only)
     // The packed per-episode counters (sf_layout.h: SF_W_*) are sized for ONE episode.  A batch without auto-reset
     // keeps ticking past game over like the bare SSF_Env / Game (ENV:246) until the caller resets, and the reference's
     // plain ints keep counting: a field that no longer fits its bits is counted here (sticky: sf_check_state) instead
@@ -1190,7 +1293,13 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     if (__ballot(ov != 0u) != 0ull)
       if (ov != 0u && real) atomicAdd(&a.acc[SF_ACC_OVERFLOW], 1ull);
   }
-  if (done && a.auto_reset) {
+  if constexpr (REPEAT) {  // this tick's share of the window's row, unless the env was parked before it
+    rp_reward += rp_parked ? 0 : r;
+    rp_events |= rp_parked ? 0u : evmask;
+    rp_w += rp_parked ? 0u : 1u;
+    rp_w |= rp_parked ? 0u : ((fort_kill ? kRpInfo : 0u) | ((S.big_hex_deaths | S.small_hex_deaths | S.shell_deaths) ? kRpDied : 0u));
+  }
+  if (REPEAT ? (done && !rp_parked) : (done && a.auto_reset)) {
     // episode totals (rl/train.py:81-88,161-164), this tick's share included
     const int ep_ret = L.ep_return, ep_kil = (int)L.ep_kills;
     const int deaths = (int)(L.c_big + L.c_small + L.c_shell);  // killShip's three call sites
@@ -1208,63 +1317,37 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     // the finished game's last observation (a.final_obs: sf_set_final_obs_output): the row SSF_Env.step returned for this
     // tick (ENV:246-253), from the state as it stands and the tick's own bearings, before the new game replaces both.  Once
     // per 5 295 ticks and lane: plain stores straight to the row, no staging
-    if (FOBS && a.final_obs != nullptr) {  // uniform
+    if ((FOBS || REPEAT) && a.final_obs != nullptr) {  // uniform
       if (real) write_obs_row(a, a.final_obs, i, L, compute_extras(a, L, a_pos, a_vel));
     }
+    if constexpr (REPEAT) {
+      // parked (see rp_w above): the rest of the window is ticks of a game in which nothing happens.  Its missiles fly on in
+      // the tile's pool, unowned (their events meet an empty mask), and leave with the new game behind the loop
+      rp_w |= kRpParked;
+      L.fl &= ~SF_FL_SHIP_ALIVE;
+      L.death_t = -(1 << 24);  // (255 ticks add 8 670)
+      L.mmask = L.smask = 0u;
+    } else {
     // a new Game (ENV:163-178).  Its missiles are gone with it: the pool entries this lane still owns leave below
     new_game(a, L);
     a_pos = sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x);
     a_vel = sf_atan2<false>(L.vy, L.vx);
-  }
-  // A lane that started a new game while others of its tile play on (only possible when episodes are out of step:
-  // sf_set_field, a reset of part of a tile) must take its entries out of the shared pool.  With every lane of the
-  // tile done in the same tick -- the regular case -- the pool is simply emptied.
-  {
-    const unsigned long long dn = __ballot(done && a.auto_reset);
-    if (dn != 0ull) {
-      if (dn == ~0ull) {
-        L.mpool = 0;
-      } else {
-        const unsigned n_before = (unsigned)__builtin_amdgcn_readfirstlane((int)L.mpool);
-        unsigned wp = 0;
-        if constexpr (SPLIT) {  // the missile wave's stores of this tick's rows are acknowledged
-          unsigned spins = 0u;
-          while (__builtin_amdgcn_readfirstlane((int)hflags[2]) == 0 && ++spins < kSpinLimit) __builtin_amdgcn_s_sleep(1);
-          if (spins >= kSpinLimit && lane == 0u) atomicAdd(&a.acc[SF_ACC_HANDOVER], 1ull);
-          asm volatile("" ::: "memory");
-        }
-#pragma unroll 1
-        for (unsigned r = 0; 64u * r < n_before; r++) {
-          const u4_t pr = __builtin_amdgcn_raw_buffer_load_b128(rs, o.o16 + r * 1024u, SF_GOFF(missile_pos, 0), 16);
-          const unsigned pm = __builtin_amdgcn_raw_buffer_load_b32(rs, o.o4 + r * 256u, SF_GOFF(missile_meta, 0), 16);
-          const bool keep = (64u * r + lane < n_before) && !((dn >> SF_MM_OWNER(pm)) & 1ull);
-          const unsigned long long kb = __ballot(keep);
-          const unsigned idx = wp + __builtin_amdgcn_mbcnt_hi((unsigned)(kb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kb, 0u));
-          wp += (unsigned)__popcll(kb);
-          sf_buf_st128<kStAux>(pr, rs, keep ? idx * 16u : SF_OOB, SF_GOFF(missile_pos, 0));
-          __builtin_amdgcn_raw_buffer_store_b32(pm, rs, keep ? idx * 4u : SF_OOB, SF_GOFF(missile_meta, 0), kStAux);
-        }
-        L.mpool = wp;
-      }
     }
   }
+  if constexpr (!REPEAT) SF_PURGE_POOL(__ballot(done && a.auto_reset))
 
   SF_STAMP(11, false);
-  if (draw_now) {  // uniform: the env's draw record (sf_drawrec.h) -- header, ship, fortress; the missiles' entries went out above
-    typedef float f4_t __attribute__((ext_vector_type(4)));
-    const sfd::Header h = sfd::make_header(L.sx, L.sy, L.angle, (L.fl & SF_FL_SHIP_ALIVE) != 0u, (L.fl & SF_FL_FORT_ALIVE) != 0u, L.fort_angle,
-                                           L.points, L.vlner, L.fort_vuln_t, L.mmask, L.smask,
-                                           (done && a.auto_reset) ? 0u : dr_proj /* a new game has no projectiles */, a.draw_pics != 0, L.time);
-    const __amdgpu_buffer_rsrc_t rs_dr = __builtin_amdgcn_make_buffer_rsrc(
-        a.draw + (size_t)__builtin_amdgcn_readfirstlane(i >> 6) * (size_t)SF_DR_TILE_BYTES, 0, SF_DR_TILE_BYTES, 0x00020000);
-    const unsigned d0 = real ? lane * (unsigned)SF_DR_LANE_STRIDE : SF_OOB;
-    sf_buf_st128<0>(u4_t{h.w[0], h.w[1], h.w[2], h.w[3]}, rs_dr, d0, 0);
-    sf_buf_st128<0>(u4_t{h.w[4], h.w[5], h.w[6], h.w[7]}, rs_dr, d0, SF_DR_PIECE_STRIDE);
-    sf_buf_st128<0>(__builtin_bit_cast(u4_t, (d2_t{L.sx, L.sy})), rs_dr, d0, (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_SHIP) * SF_DR_PIECE_STRIDE);
-  }
+  if constexpr (!REPEAT)
+    if (draw_now) SF_DRAW_HEADER(done && a.auto_reset, dr_proj)  // uniform
   if (!FUSED) store_lane_buf(rs, o, L);
   SF_STAMP(14, false);
 
+  if constexpr (REPEAT) {
+    rp_apos = a_pos;
+    rp_avel = a_vel;
+    rp_proj = dr_proj;
+    if (__ballot(!(rp_w & kRpParked)) == 0ull) break;  // uniform: every env of the tile is parked (batches run in lockstep)
+  } else {
   if (real) {
     if (reward_out) SF_ST(int32_t, (unsigned char*)(reward_out + so), g.o4, r);
     if (done_out) SF_ST(uint8_t, (unsigned char*)(done_out + so), g.o1, (uint8_t)done);
@@ -1289,28 +1372,7 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
     }
   }
   SF_STAMP(7, false);
-  if constexpr (OBSK == 1) {  // the host guarantees: features, float32, n_envs % 64 == 0, aligned output (sf_launch_step)
-    constexpr int DIM = AUTOTURN ? 17 : 19;
-    float* stage = reinterpret_cast<float*>(lds + kLdsStage);
-    const Extras e = SPLIT ? compute_extras(a, L, a_pos, a_vel, kc) : compute_extras(a, L, a_pos, a_vel);
-    write_features_f32<DIM>(stage + tid * DIM, L, e, a.real_shell_count);
-    if ((i & ~63u) < (unsigned)n_envs_p)  // the padding waves behind the batch write nothing
-      flush_features_f32<DIM>(stage + (tid & ~63u) * DIM, (float*)obs + (so + (i & ~63u)) * DIM, lane);
-  } else if (obs != nullptr && a.obs_type != 3) {  // uniform across the grid
-    Extras e = compute_extras(a, L, a_pos, a_vel);
-    if (a.ref_reset_obs && done && a.auto_reset) e = Extras{0.0, 0.0, 0.0};  // (a new game's observation as the reference returns it: sf_launch_step keeps such batches here)
-    if (a.obs_f64) {
-      double* stage = lds + kLdsStage;
-      write_obs<double>(a, stage + tid * a.obs_dim, L, e);
-      flush_obs_wave<double>(a, stage + (tid & ~63u) * a.obs_dim, (double*)obs + so * a.obs_dim, i & ~63u, lane,
-                             obs_vec_ok);
-    } else {
-      float* stage = reinterpret_cast<float*>(lds + kLdsStage);
-      write_obs<float>(a, stage + tid * a.obs_dim, L, e);
-      flush_obs_wave<float>(a, stage + (tid & ~63u) * a.obs_dim, (float*)obs + so * a.obs_dim, i & ~63u, lane,
-                            obs_vec_ok);
-    }
-  }
+  SF_WRITE_OBSERVATION(so, a_pos, a_vel, done && a.auto_reset)
   if constexpr (OBSK != 1) {
     // image batches: which ships died this tick, one word per tile.  sf_render_kernel starts those frames first (the
     // first frame of an explosion costs three ordinary ones, sf_render.hip); a scheduling hint, nothing else reads it
@@ -1332,9 +1394,42 @@ __global__ __launch_bounds__(BLKP > 1000 ? 2 * (BLKP - 1000) : BLKP) void sf_ste
       norm_partials_wave<float>(a, reinterpret_cast<float*>(lds + kLdsStage) + (size_t)(tid & ~63u) * a.obs_dim, i & ~63u,
                                 lane, my_ret, has_obs);
   }
+  }  // (!REPEAT)
   }  // tick loop
+  if constexpr (REPEAT) {
+    // the parked envs' new games (ENV:163-178; rl/train.py:80), of which no tick is played in this launch; their missiles --
+    // the finished games' -- leave the tile's pool
+    const bool parked = (rp_w & kRpParked) != 0u;
+    const unsigned long long pk = __ballot(parked);
+    if (pk != 0ull) {
+      if (parked) {
+        new_game(a, L);
+        rp_apos = sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x);
+        rp_avel = sf_atan2<false>(L.vy, L.vx);
+      }
+      SF_PURGE_POOL(pk)
+    }
+  }
   if (FUSED) store_lane_buf(rs, o, L);
-  if (XTRA && act_type == SF_ACT_SAMPLED && lane == 0)  // the tile's tick counter moves on by the ticks of this launch
+  if constexpr (REPEAT) {  // the window's one row (a.act_out: the ticks played, sf_launch_step_repeat)
+    const bool parked = (rp_w & kRpParked) != 0u;
+    if (OBSK != 1 && a.draw != nullptr) SF_DRAW_HEADER(parked, rp_proj)  // uniform
+    if (real) {
+      if (reward_out) SF_ST(int32_t, (unsigned char*)reward_out, g.o4, rp_reward);
+      if (done_out) SF_ST(uint8_t, (unsigned char*)done_out, g.o1, (uint8_t)parked);
+      if (info_out) SF_ST(uint8_t, (unsigned char*)info_out, g.o1, (uint8_t)((rp_w & kRpInfo) != 0u));
+      if (a.events) SF_ST(uint32_t, (unsigned char*)a.events, g.o4, rp_events);
+      if (a.act_out) SF_ST(uint8_t, (unsigned char*)a.act_out, g.o1, (uint8_t)(rp_w & 0xFFu));
+    }
+    SF_WRITE_OBSERVATION((size_t)0, rp_apos, rp_avel, parked)
+    if constexpr (OBSK != 1) {
+      if (a.hint) {  // uniform: the ships that died in ANY tick of the window (it only decides when a frame is drawn)
+        const unsigned long long died = __ballot(real && (rp_w & kRpDied) != 0u);
+        if (lane == 0) a.hint[i >> 6] = died;
+      }
+    }
+  }
+  if (XTRA && !REPEAT && act_type == SF_ACT_SAMPLED && lane == 0)  // the tile's tick counter moves on by the ticks of this launch
     reinterpret_cast<unsigned*>(const_cast<void*>(actions))[4 * (size_t)(i >> 6)] = act_rec.x + (unsigned)n_iter;
   SF_STAMP(8, false);
   SF_STAMP(9, true);
@@ -1431,5 +1526,37 @@ hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, con
 #undef SF_GO1
 #undef SF_GO_SPLIT
 #undef SF_GO2
+  return hipGetLastError();
+}
+
+// sf_step_repeat (sfmi_repeat.h): `repeat` ticks of one action per env in ONE launch of a REPEAT instantiation (BLKP = 2000 +
+// SF_BLOCK; sf_step_kernel), one row of outputs; `ticks` (uint8 [n_envs], may be null) travels in a.act_out, which no REPEAT
+// launch uses for anything else.  The batch auto-resets (the caller checked).
+hipError_t sf_launch_step_repeat(const SfKernelArgs& a0, bool autoturn, bool shaped, const void* actions, int act_type, void* obs,
+                                 int32_t* reward, uint8_t* done, uint8_t* info, uint8_t* ticks, int repeat, hipStream_t stream) {
+  SfKernelArgs a = a0;
+  a.act_out = ticks;
+  const size_t elem = a.obs_f64 ? sizeof(double) : sizeof(float);
+  const int vec_ok = ((uintptr_t)obs & 15u) == 0;  // (one row of observations: row 0)
+  const bool fast_obs = obs != nullptr && a.obs_type == 0 && !a.obs_f64 && vec_ok && a.n_envs % 64 == 0 &&
+                        a.obs_dim == (autoturn ? 17 : 19) && !a.ref_reset_obs;
+  const unsigned grid = (unsigned)(a.lanes / SF_BLOCK);
+  const size_t lds_bytes = (size_t)(SF_LDS_DOUBLES + SF_BLOCK + SF_ATAB_DOUBLES) * sizeof(double) + (size_t)SF_BLOCK * a.obs_dim * elem;
+#define SF_GO(AT, SH)                                                                                                       \
+  do {                                                                                                                      \
+    if (fast_obs)                                                                                                           \
+      hipLaunchKernelGGL((sf_step_kernel<AT, SH, true, 1, true, 2000 + SF_BLOCK, false>), dim3(grid), dim3(SF_BLOCK), lds_bytes, \
+                         stream, a.state, a.consts, actions, a.n_envs, act_type, reward, done, info, a, obs, vec_ok, repeat);  \
+    else                                                                                                                    \
+      hipLaunchKernelGGL((sf_step_kernel<AT, SH, true, 0, true, 2000 + SF_BLOCK, false>), dim3(grid), dim3(SF_BLOCK), lds_bytes, \
+                         stream, a.state, a.consts, actions, a.n_envs, act_type, reward, done, info, a, obs, vec_ok, repeat);  \
+  } while (0)
+  switch ((autoturn ? 2 : 0) | (shaped ? 1 : 0)) {
+    case 0: SF_GO(false, false); break;
+    case 1: SF_GO(false, true); break;
+    case 2: SF_GO(true, false); break;
+    default: SF_GO(true, true); break;
+  }
+#undef SF_GO
   return hipGetLastError();
 }

@@ -327,6 +327,7 @@ struct SfKernelArgs {
   // image batches only: per tile, the envs whose ship died in the last tick (sf_render_kernel's launch order); else null
   unsigned long long* hint;
   // optional: the action every env played this tick as uint8 [n_steps][n_envs] (the sampled ones of sf_step_sampled); else null
+  // (a REPEAT launch, sf_step_repeat: the ticks every env played in the window, uint8 [n_envs]; else null)
   unsigned char* act_out;
   // image batches only: the envs' draw records (sf_drawrec.h), SF_DR_BYTES per lane, written by the step kernel for the frame
   // kernel; else null.  draw_pics: the batch's render pictures exist (the records' decisions depend on it)

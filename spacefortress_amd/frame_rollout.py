@@ -161,9 +161,12 @@ class FrameRollout(DeviceRollout):
 
     def _step_record(self, ap, at, step, stream):
         e, P = self.env, self._ptr
-        # the step's done bytes are the start flags of frame step + 1: the kernel writes them straight into their row
-        _lib.check(self._L.sf_step_record(e._h, ap, at, None, P["r"], P["start"][step + 1], P["i"], P["rew"][step],
-                                          P["mask"][step + 1], P["ep"], P["fin"], P["act"][step], stream))
+        if e.frame_skip > 1:  # the env's action repeat: DeviceRollout._repeat_record, the done bytes into the flags' row
+            self._repeat_record(ap, at, step, None, P["start"][step + 1], stream)
+        else:
+            # the step's done bytes are the start flags of frame step + 1: the kernel writes them straight into their row
+            _lib.check(self._L.sf_step_record(e._h, ap, at, None, P["r"], P["start"][step + 1], P["i"], P["rew"][step],
+                                              P["mask"][step + 1], P["ep"], P["fin"], P["act"][step], stream))
         self._done = self._start_rows[step + 1]  # (what step() hands to the env's recording / duration hooks)
         _lib.check(self._L.sf_render(e._h, _lib.OBS_TYPES["image"], P["row"][step + 1], self._env_stride, stream))
         self._gather(None, e.num_envs, step + 1, self._cur)

@@ -51,9 +51,17 @@ class FrameStack:
         episode."""
         e = self.env
         at = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}[actions.dtype]
-        e._before_step(actions)
-        _lib.check(e._L.sf_step(e._h, C.c_void_p(actions.data_ptr()), at, None, C.c_void_p(self._rew.data_ptr()),
-                                C.c_void_p(self._done.data_ptr()), C.c_void_p(self._info.data_ptr()), e._stream()))
+        if e.frame_skip > 1:  # the env's action repeat (sfmi_repeat.h): frame_skip ticks without a frame, then the one below
+            e._no_duration_log("step_repeat()")
+            ticks = e._ticks_buffer()
+            _lib.check(e._L.sf_step_repeat(e._h, C.c_void_p(actions.data_ptr()), at, e.frame_skip, None,
+                                           C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
+                                           C.c_void_p(self._info.data_ptr()), C.c_void_p(ticks.data_ptr()), e._stream()))
+            e.last_ticks = ticks
+        else:
+            e._before_step(actions)
+            _lib.check(e._L.sf_step(e._h, C.c_void_p(actions.data_ptr()), at, None, C.c_void_p(self._rew.data_ptr()),
+                                    C.c_void_p(self._done.data_ptr()), C.c_void_p(self._info.data_ptr()), e._stream()))
         e._stepped(actions, self._rew, self._done, self._info)
         # the new frame into the next slot; finished envs get their other slots zeroed by the same launch
         # (current_obs *= masks, rl/train.py:92-93)

@@ -135,8 +135,24 @@ class DeviceRollout:
         P = self._ptr
         stream = self._stream()
         ap, at = C.c_void_p(a.data_ptr()), a.element_size()
-        e._before_step(a)
-        if self.norm is not None:
+        if e.frame_skip > 1:
+            e._no_duration_log("step_repeat()")
+        else:
+            e._before_step(a)
+        if self.norm is not None and e.frame_skip > 1:
+            # the env's action repeat behind VecNormalize: sf_step_repeat, the stand-alone normaliser on the window's
+            # observation and summed reward (SFVecNormalize's unfused branch), then the bookkeeping on the normalised reward
+            z = self.norm
+            if not (z.ob and z.ret_on):
+                raise NotImplementedError("DeviceRollout drives VecNormalize(ob=True, ret=True), the trainer's configuration")
+            ticks = e._ticks_buffer()
+            _lib.check(self._L.sf_step_repeat(e._h, ap, at, e.frame_skip, P["obs"][step + 1], P["r"], P["d"], P["i"],
+                                              C.c_void_p(ticks.data_ptr()), stream))
+            e.last_ticks = ticks
+            z._filter(self.observations[step + 1], self._rew)
+            _lib.check(self._L.sf_record_step_f32(e.num_envs, C.c_void_p(z._rew.data_ptr()), P["d"], P["rew"][step],
+                                                  P["mask"][step + 1], P["ep"], P["fin"], ap, at, P["act"][step], stream))
+        elif self.norm is not None:
             z = self.norm
             if not (z.ob and z.ret_on):
                 raise NotImplementedError("DeviceRollout drives VecNormalize(ob=True, ret=True), the trainer's configuration")
@@ -155,8 +171,30 @@ class DeviceRollout:
             self.states[step + 1].copy_(state)
         return self._views[step]
 
+    def _repeat_record(self, ap, at, step, obs, done, stream):
+        """The env's action repeat (sfmi_repeat.h): sf_step_repeat, then the stand-alone sf_record_step on the window's summed
+        reward -- two launches, the same float32 bookkeeping on the same values as sf_step_record's epilogue."""
+        e, P = self.env, self._ptr
+        ticks = e._ticks_buffer()
+        _lib.check(self._L.sf_step_repeat(e._h, ap, at, e.frame_skip, obs, P["r"], done, P["i"], C.c_void_p(ticks.data_ptr()),
+                                          stream))
+        e.last_ticks = ticks
+        _lib.check(self._L.sf_record_step(e.num_envs, P["r"], done, P["rew"][step], P["mask"][step + 1], P["ep"], P["fin"], ap, at,
+                                          P["act"][step], stream))
+
     def _step_record(self, ap, at, step, stream):
         e, P = self.env, self._ptr
+        if e.frame_skip > 1 and self.num_stack > 1:
+            self._repeat_record(ap, at, step, None, P["d"], stream)
+            if e.default_geometry:
+                _lib.check(self._L.sf_render_shift(e._h, P["obs"][step], P["obs"][step + 1], self.num_stack, P["d"], stream))
+            else:
+                self.observations[step + 1][:, :-1].copy_(self.observations[step][:, 1:])
+                _lib.check(self._L.sf_render_stack(e._h, P["obs"][step + 1], self.num_stack, self.num_stack - 1, P["d"], stream))
+            return
+        if e.frame_skip > 1:
+            self._repeat_record(ap, at, step, P["obs"][step + 1], P["d"], stream)
+            return
         if self.num_stack > 1:
             # the step without an observation, then ONE render launch builds observations[step + 1] from
             # observations[step]: shift by a frame, zero the finished envs, new frame last

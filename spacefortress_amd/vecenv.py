@@ -35,9 +35,25 @@ _UNSIGNED_FIELDS = {"spawn_cursor", "missile_mask", "shell_mask", "flags"}
 class SFVecEnv:
     def __init__(self, num_envs, gametype="youturn", obs_type="features", action_set=1, device=None,
                  seed=1, spawn_skip=0, spawn_stride=0, obs_dtype=torch.float32, faithful_bugs=True,
-                 auto_reset=True, spawn_table_len=0, reuse_buffers=False, image_geometry=None, ref_reset_obs=False):
+                 auto_reset=True, spawn_table_len=0, reuse_buffers=False, image_geometry=None, ref_reset_obs=False,
+                 frame_skip=1):
         if obs_type not in _lib.OBS_TYPES:
             raise AssertionError("obs_type %r" % (obs_type,))  # ENV:51
+        # action repeat (sfmi_repeat.h: sf_step_repeat): every step / step_tensors / step_async plays its action for up to
+        # frame_skip ticks in one launch; an env that finishes inside the window stops there.  The episode log then counts
+        # lengths and fire actions in AGENT steps (one row per window).  1: a tick per step, the calls as they always were.
+        # Fixed at construction: with K > 1 the instance's step_tensors IS the repeat (bound below), so that the plain step's
+        # host path -- one Python call per launch, barely ahead of a 6 us kernel -- carries no test for it
+        self.frame_skip = int(frame_skip)
+        if not 1 <= self.frame_skip <= 255:
+            raise ValueError("frame_skip must be in [1, 255] (got %r)" % (frame_skip,))
+        if self.frame_skip > 1 and not auto_reset:
+            raise ValueError("frame_skip > 1 needs auto_reset=True: a finished env of a batch without auto-reset would have to be "
+                             "frozen in place for the rest of the window (sfmi_repeat.h)")
+        self.last_ticks = None  # uint8 [N]: the ticks every env played in the last step_repeat call
+        self._own_ticks = None
+        if self.frame_skip > 1:
+            self.step_tensors = self._step_tensors_skip
         self._L = _lib.lib()
         if not torch.cuda.is_available():
             raise _lib.SfmiError("SFVecEnv needs a HIP device (torch.cuda.is_available() is False); "
@@ -207,6 +223,55 @@ class SFVecEnv:
         self._stepped(actions, bufs[1], bufs[2], bufs[3])
         return bufs
 
+    def _step_tensors_skip(self, actions, out=None):
+        """step_tensors of a batch made with frame_skip > 1: the action repeated for frame_skip ticks (step_repeat)."""
+        return self.step_repeat(actions, self.frame_skip, out=out)
+
+    def _ticks_buffer(self, ticks_out=None):
+        """The uint8 [N] tensor a step_repeat call writes the played ticks into: `ticks_out`, or the env's own (made once)."""
+        if ticks_out is None:
+            if self._own_ticks is None:
+                self._own_ticks = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
+            return self._own_ticks
+        if not (torch.is_tensor(ticks_out) and ticks_out.device == self.device and ticks_out.dtype == torch.uint8
+                and ticks_out.is_contiguous() and ticks_out.numel() == self.num_envs):
+            raise ValueError("ticks_out must be a contiguous uint8 tensor of %d elements on %s" % (self.num_envs, self.device))
+        return ticks_out
+
+    def step_repeat(self, actions, repeat, out=None, ticks_out=None):
+        """One agent step that plays `actions` for up to `repeat` ticks in ONE launch (sfmi_repeat.h: sf_step_repeat; image
+        batches: and one frame).  Returns (obs, reward, done, info) like `step_tensors`: the observation of the state the window
+        leaves (a finished env's: its new game's first one), the int32 sum of the played ticks' rewards, done, the OR of the
+        ticks' info.  An env whose game ends inside the window stops there -- its new game is not played on with the old
+        action -- and `self.last_ticks` (uint8 [N]; `ticks_out` if given) says how many ticks each env played.  With events
+        enabled `self.events` holds the OR of the played ticks' masks.  The episode log gets ONE row per call: lengths and fire
+        actions in agent steps.  1 <= repeat <= 255; repeat == 1 is step_tensors.  ValueError on an auto_reset=False batch;
+        RuntimeError for repeat > 1 while a duration log is enabled (it follows single ticks) or during a recording (a replay
+        file has no field for it)."""
+        if actions.device != self.device or not actions.is_contiguous() or actions.numel() != self.num_envs:
+            raise ValueError("actions must be a contiguous tensor of %d elements on %s" % (self.num_envs, self.device))
+        at = _ACT_TYPES.get(actions.dtype)
+        if at is None:
+            raise TypeError("actions dtype must be uint8, int32 or int64 (got %s)" % (actions.dtype,))
+        repeat = int(repeat)
+        if repeat != 1:
+            self._no_duration_log("step_repeat()")
+        if self._rec is not None and repeat > 1:
+            raise RuntimeError("step_repeat() during a recording: a replay file has no field for an action repeat")
+        ticks = self._ticks_buffer(ticks_out)
+        if out is None and self._bufs is not None and self.reuse_buffers:
+            bufs, ptrs = self._bufs, self._buf_ptrs
+        else:
+            bufs = out if out is not None else self._alloc()
+            ptrs = tuple(C.c_void_p(t.data_ptr()) for t in bufs)
+        if repeat == 1:
+            self._before_step(actions)  # (sf_step itself: a duration log follows it)
+        _lib.check(self._L.sf_step_repeat(self._h, C.c_void_p(actions.data_ptr()), at, repeat, ptrs[0], ptrs[1], ptrs[2], ptrs[3],
+                                          C.c_void_p(ticks.data_ptr()), self._stream()))
+        self.last_ticks = ticks
+        self._stepped(actions, bufs[1], bufs[2], bufs[3])
+        return bufs
+
     def rollout(self, actions, out=None, want_obs=True):
         """K steps whose actions are all known up front, fused into one launch (sfmi.h: sf_rollout).
         `actions`: contiguous uint8/int32/int64 tensor [K, N] on this device.  Returns
@@ -293,6 +358,8 @@ class SFVecEnv:
         sf_create leaves (the reference has no way to put a Game into a given state either)."""
         from .replay import Recorder
 
+        if self.frame_skip > 1:
+            raise RuntimeError("start_recording() on a batch with frame_skip > 1: a replay file has no field for an action repeat")
         if not self._fresh:
             raise RuntimeError("start_recording() needs a new batch (nothing stepped, reset or edited since SFVecEnv(...))")
         self._rec = Recorder(self)

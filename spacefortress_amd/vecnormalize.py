@@ -76,7 +76,7 @@ class SFVecNormalize:
 
     def step_tensors(self, actions):
         v = self.venv
-        if not (self.ob and self.ret_on) or not hasattr(v, "_alloc"):
+        if not (self.ob and self.ret_on) or not hasattr(v, "_alloc") or getattr(v, "frame_skip", 1) > 1:  # (an action repeat: the env's own step)
             obs, rew, done, info = v.step_tensors(actions)
             obs, rew = self._filter(obs, rew)
             return obs, rew, done, info
