@@ -233,6 +233,33 @@ def check(rc):
     raise SfmiError("libsfmi: %s (status %d)" % (msg, rc))
 
 
+def ptr(t):
+    """The address of a tensor for the C ABI; None stays None (an optional output)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def act_types():
+    """torch dtype of an action tensor -> SF_ACT_* (sfmi.h: the element size); THE table, read once by SFVecEnv's module."""
+    import torch
+    return {torch.uint8: 1, torch.int32: ACT_I32, torch.int64: ACT_I64}
+
+
+def score_glyphs(alpha, layout, x0):
+    """(ScoreGlyphs, the uint8 [11, gh, gw] array to pass beside it) of an atlas as score_glyphs() gives it: alpha, layout =
+    (gw, gh, advance, y0), x0 int [11, 10] or one int.  Keep both alive across the call that takes their addresses."""
+    import numpy as np
+    a = np.ascontiguousarray(alpha, np.uint8)
+    gw, gh, adv, y0 = (int(v) for v in layout)
+    if a.shape != (11, gh, gw):
+        raise ValueError("alpha must be uint8 [11, gh, gw] = [11, %d, %d]" % (gh, gw))
+    g = ScoreGlyphs(gw, gh, adv, y0)
+    xs = np.broadcast_to(np.asarray(x0, np.int16), (11, 10))
+    for i in range(11):
+        for j in range(10):
+            g.x0[i][j] = int(xs[i, j])
+    return g, a
+
+
 def raw_stream(device):
     """The current HIP stream of `device` as a ctypes pointer.  torch.cuda.current_stream(...).cuda_stream builds a
     Stream object per call (4 us of the 8 us a step launch costs on the host); the raw getter does not."""

@@ -277,6 +277,8 @@ struct StepLaunch {
   int32_t* reward = nullptr;
   uint8_t* done = nullptr;
   uint8_t* info = nullptr;
+  int repeat = 1;            // > 1: ONE launch plays every env's action for up to `repeat` ticks (sf_step_repeat)
+  uint8_t* ticks = nullptr;  // ... and says here how many each env played
   // optional patches to the batch's SfKernelArgs
   float *t_reward = nullptr, *t_mask = nullptr, *t_episode = nullptr, *t_final = nullptr;  // trainer outputs (sf_step_record)
   int64_t* t_actions = nullptr;
@@ -293,7 +295,7 @@ static int check_act_type(const char* who, int act_type) {
   return SF_OK;
 }
 
-// guard -> flush -> launch -> draw_current -> frames: the one path from an entry point to sf_launch_step
+// guard -> flush -> launch -> draw_current -> frames: the one path from an entry point to sf_launch_step / sf_launch_step_repeat
 static int launch_steps(sf_batch* b, const StepLaunch& d, void* obs_dev, void* stream) {
   DeviceGuard guard(b->device);
   const bool image = sfb_is_image(b), sampled = d.act_type == SF_ACT_SAMPLED;
@@ -313,6 +315,13 @@ static int launch_steps(sf_batch* b, const StepLaunch& d, void* obs_dev, void* s
   }
   const void* actions = sampled ? b->d_actrec.get() : d.actions;
   SF_FLUSH_VIEW(b, stream);
+  if (d.repeat > 1) {  // one REPEAT launch; an image batch's frame: one sfb_render from the draw records it left
+    HIP_TRY(sf_launch_step_repeat(args, b->autoturn, b->preset.shaped != 0, actions, d.act_type, image ? nullptr : obs_dev, d.reward,
+                                  d.done, d.info, d.ticks, d.repeat, (hipStream_t)stream));
+    b->draw_current = b->args.draw != nullptr;  // (the draw records of the state the window ends in)
+    if (image && obs_dev) return sfb_render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
+    return SF_OK;
+  }
   if (!(image && obs_dev)) {
     HIP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, actions, d.act_type, image ? nullptr : obs_dev, d.reward,
                            d.done, d.info, d.n_steps, d.fused, (hipStream_t)stream));
@@ -367,21 +376,12 @@ extern "C" int sf_step_repeat(sf_batch* b, const void* actions_dev, int act_type
                  "would have to be frozen in place, and a parked lane is given its new game; step such a batch tick by tick");
     return SF_ERR_ARG;
   }
-  if (repeat == 1) {  // sf_step itself; every env plays its one tick
-    StepLaunch d{"sf_step_repeat", actions_dev, act_type, 1, false, reward_dev, done_dev, info_dev};
-    const int rc = launch_steps(b, d, obs_dev, stream);
-    if (rc != SF_OK) return rc;
-    DeviceGuard guard(b->device);
-    if (ticks_dev) HIP_TRY(hipMemsetAsync(ticks_dev, 1, (size_t)b->n_envs, (hipStream_t)stream));
-    return SF_OK;
-  }
+  StepLaunch d{"sf_step_repeat", actions_dev, act_type, 1, false, reward_dev, done_dev, info_dev, repeat, ticks_dev};
+  const int rc = launch_steps(b, d, obs_dev, stream);
+  if (rc != SF_OK || repeat > 1) return rc;
+  // repeat == 1 was sf_step itself; every env played its one tick
   DeviceGuard guard(b->device);
-  const bool image = sfb_is_image(b);
-  SF_FLUSH_VIEW(b, stream);
-  HIP_TRY(sf_launch_step_repeat(b->args, b->autoturn, b->preset.shaped != 0, actions_dev, act_type, image ? nullptr : obs_dev,
-                                reward_dev, done_dev, info_dev, ticks_dev, repeat, (hipStream_t)stream));
-  b->draw_current = b->args.draw != nullptr;  // (an image batch's launch leaves the draw records of the state the window ends in)
-  if (image && obs_dev) return sfb_render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
+  if (ticks_dev) HIP_TRY(hipMemsetAsync(ticks_dev, 1, (size_t)b->n_envs, (hipStream_t)stream));
   return SF_OK;
 }
 

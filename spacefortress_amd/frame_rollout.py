@@ -19,7 +19,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .rollout import DeviceRollout, _p
+from ._lib import ptr
+from .rollout import DeviceRollout
 
 FRAME = _lib.IMAGE_OUT * _lib.IMAGE_OUT
 _OUT_TYPES = {torch.uint8: _lib.STACK_U8, torch.float16: _lib.STACK_F16, torch.float32: _lib.STACK_F32}
@@ -40,7 +41,7 @@ def gather_stacks(frames_ptr, start_ptr, n_envs, rows, num_stack, env_stride, ro
         if n_samples == 0:  # (an empty tensor has no address, and a NULL index means "one step")
             return
     _lib.check(_lib.lib().sf_gather_stacks(frames_ptr, start_ptr, n_envs, rows, num_stack, env_stride, row_stride,
-                                           _p(index), it, n_samples, step, _p(out), ot, stream))
+                                           ptr(index), it, n_samples, step, ptr(out), ot, stream))
 
 
 def gather_errors(device, clear=False):
@@ -159,15 +160,10 @@ class FrameRollout(DeviceRollout):
         # what step() returns: the current stack lives in ONE reused buffer (the next step overwrites it)
         self._views = [(self._cur, self.rewards[t], self.masks[t + 1]) for t in range(T)]
 
-    def _step_record(self, ap, at, step, stream):
+    def _step_record(self, a, ap, at, step, stream):
         e, P = self.env, self._ptr
-        if e.frame_skip > 1:  # the env's action repeat: DeviceRollout._repeat_record, the done bytes into the flags' row
-            self._repeat_record(ap, at, step, None, P["start"][step + 1], stream)
-        else:
-            # the step's done bytes are the start flags of frame step + 1: the kernel writes them straight into their row
-            _lib.check(self._L.sf_step_record(e._h, ap, at, None, P["r"], P["start"][step + 1], P["i"], P["rew"][step],
-                                              P["mask"][step + 1], P["ep"], P["fin"], P["act"][step], stream))
-        self._done = self._start_rows[step + 1]  # (what step() hands to the env's recording / duration hooks)
+        # the step's done bytes are the start flags of frame step + 1: the kernel writes them straight into their row
+        self._step_and_record(a, ap, at, step, None, self._start_rows[step + 1], P["start"][step + 1], stream)
         _lib.check(self._L.sf_render(e._h, _lib.OBS_TYPES["image"], P["row"][step + 1], self._env_stride, stream))
         self._gather(None, e.num_envs, step + 1, self._cur)
 

@@ -7,8 +7,6 @@ frame (`current_obs[:, :-1] = current_obs[:, 1:]`), zeroes the whole stack of fi
 straight into the ring slot (sfmi.h: env_stride), finished envs are zeroed with one masked fill, and
 `stacked()` gives the frames in the reference's order (oldest first) when a consumer wants them so.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -26,6 +24,8 @@ class FrameStack:
         self._rew = torch.empty(n, dtype=torch.int32, device=env.device)
         self._done = torch.empty(n, dtype=torch.uint8, device=env.device)
         self._info = torch.empty(n, dtype=torch.uint8, device=env.device)
+        self._ptrs = (None, _lib.ptr(self._rew), _lib.ptr(self._done), _lib.ptr(self._info))  # (no observation: sf_render_stack)
+        self._ring_ptr = _lib.ptr(self.ring)
 
     def __getattr__(self, name):
         if name == "reset_lanes":  # (not forwarded to the env: see _lib.NO_RESET_LANES)
@@ -50,24 +50,12 @@ class FrameStack:
         next step overwrites; the stack is updated in place: finished envs keep only the first frame of their next
         episode."""
         e = self.env
-        at = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}[actions.dtype]
-        if e.frame_skip > 1:  # the env's action repeat (sfmi_repeat.h): frame_skip ticks without a frame, then the one below
-            e._no_duration_log("step_repeat()")
-            ticks = e._ticks_buffer()
-            _lib.check(e._L.sf_step_repeat(e._h, C.c_void_p(actions.data_ptr()), at, e.frame_skip, None,
-                                           C.c_void_p(self._rew.data_ptr()), C.c_void_p(self._done.data_ptr()),
-                                           C.c_void_p(self._info.data_ptr()), C.c_void_p(ticks.data_ptr()), e._stream()))
-            e.last_ticks = ticks
-        else:
-            e._before_step(actions)
-            _lib.check(e._L.sf_step(e._h, C.c_void_p(actions.data_ptr()), at, None, C.c_void_p(self._rew.data_ptr()),
-                                    C.c_void_p(self._done.data_ptr()), C.c_void_p(self._info.data_ptr()), e._stream()))
-        e._stepped(actions, self._rew, self._done, self._info)
+        # the agent step without a frame (the env's frame_skip ticks), then the one frame below
+        e._step_into(actions, e._act_type(actions), self._ptrs, self._rew, self._done, self._info)
         # the new frame into the next slot; finished envs get their other slots zeroed by the same launch
         # (current_obs *= masks, rl/train.py:92-93)
         self.head = (self.head + 1) % self.num_stack
-        _lib.check(e._L.sf_render_stack(e._h, C.c_void_p(self.ring.data_ptr()), self.num_stack, self.head,
-                                        C.c_void_p(self._done.data_ptr()), e._stream()))
+        _lib.check(e._L.sf_render_stack(e._h, self._ring_ptr, self.num_stack, self.head, self._ptrs[2], e._stream()))
         return self._rew, self._done.view(torch.bool), self._info.view(torch.bool)  # 0 / 1 bytes: a view, not a kernel
 
     def stacked(self):

@@ -22,10 +22,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from ._lib import ptr
 
 
 class DeviceRollout:
@@ -95,10 +92,10 @@ class DeviceRollout:
         if self.num_stack > 1:  # update_current_obs on a zeroed stack (rl/train.py:43,60-62)
             _lib.check(e._L.sf_reset(e._h, None, e._stream()))
             self.observations[0].zero_()
-            _lib.check(e._L.sf_render_stack(e._h, _p(self.observations[0]), self.num_stack, self.num_stack - 1, None,
+            _lib.check(e._L.sf_render_stack(e._h, ptr(self.observations[0]), self.num_stack, self.num_stack - 1, None,
                                             e._stream()))
             return self.observations[0]
-        _lib.check(e._L.sf_reset(e._h, _p(self.observations[0]), e._stream()))
+        _lib.check(e._L.sf_reset(e._h, ptr(self.observations[0]), e._stream()))
         if self.norm is not None:
             self.norm._filter(self.observations[0], None)  # VecNormalize.reset: update + normalise in place
         return self.observations[0]
@@ -122,47 +119,28 @@ class DeviceRollout:
     def step(self, step, action, value_pred=None, action_log_prob=None, state=None):
         """envs.step(action) + the bookkeeping + rollouts.insert(...) of rl/train.py:79-98.
         `action`: [N] or [N, 1] integer tensor on the device."""
-        e = self.env
+        e, z = self.env, self.norm
         a = action
         if a.dtype not in (torch.uint8, torch.int32, torch.int64):
             a = a.long()
         if not a.is_contiguous():
             a = a.contiguous()
-        if a.numel() != e.num_envs or a.device != e.device:
-            raise ValueError("action must hold %d elements on %s" % (e.num_envs, e.device))
+        at = e._act_type(a)
+        if z is not None and not (z.ob and z.ret_on):
+            raise NotImplementedError("DeviceRollout drives VecNormalize(ob=True, ret=True), the trainer's configuration")
         if self._ptr is None:
             self._pointers()
         P = self._ptr
         stream = self._stream()
-        ap, at = C.c_void_p(a.data_ptr()), a.element_size()
-        if e.frame_skip > 1:
-            e._no_duration_log("step_repeat()")
+        ap = C.c_void_p(a.data_ptr())
+        if z is None:
+            self._step_record(a, ap, at, step, stream)
         else:
-            e._before_step(a)
-        if self.norm is not None and e.frame_skip > 1:
-            # the env's action repeat behind VecNormalize: sf_step_repeat, the stand-alone normaliser on the window's
-            # observation and summed reward (SFVecNormalize's unfused branch), then the bookkeeping on the normalised reward
-            z = self.norm
-            if not (z.ob and z.ret_on):
-                raise NotImplementedError("DeviceRollout drives VecNormalize(ob=True, ret=True), the trainer's configuration")
-            ticks = e._ticks_buffer()
-            _lib.check(self._L.sf_step_repeat(e._h, ap, at, e.frame_skip, P["obs"][step + 1], P["r"], P["d"], P["i"],
-                                              C.c_void_p(ticks.data_ptr()), stream))
-            e.last_ticks = ticks
-            z._filter(self.observations[step + 1], self._rew)
-            _lib.check(self._L.sf_record_step_f32(e.num_envs, C.c_void_p(z._rew.data_ptr()), P["d"], P["rew"][step],
-                                                  P["mask"][step + 1], P["ep"], P["fin"], ap, at, P["act"][step], stream))
-        elif self.norm is not None:
-            z = self.norm
-            if not (z.ob and z.ret_on):
-                raise NotImplementedError("DeviceRollout drives VecNormalize(ob=True, ret=True), the trainer's configuration")
-            _lib.check(self._L.sf_step_normalize(e._h, z._h, ap, at, P["obs"][step + 1], P["r"], P["d"], P["i"],
-                                                 C.c_void_p(z._rew.data_ptr()), 0 if z.training else 1, stream))
-            _lib.check(self._L.sf_record_step_f32(e.num_envs, C.c_void_p(z._rew.data_ptr()), P["d"], P["rew"][step],
-                                                  P["mask"][step + 1], P["ep"], P["fin"], ap, at, P["act"][step], stream))
-        else:
-            self._step_record(ap, at, step, stream)
-        e._stepped(a, self._rew, self._done, self._info)  # (the engine's own int reward, whatever VecNormalize makes of it)
+            # observation and reward through the normaliser (SFVecNormalize._step_into), then the bookkeeping on the normalised
+            # reward; the hooks see the engine's own int reward, whatever VecNormalize makes of it
+            z._step_into(a, at, self._views[step][0], (P["obs"][step + 1], P["r"], P["d"], P["i"]), self._rew, self._done,
+                         self._info)
+            self._record(self._L.sf_record_step_f32, ptr(z._rew), P["d"], ap, at, step, stream)
         if value_pred is not None:
             self.value_preds[step].copy_(value_pred)
         if action_log_prob is not None:
@@ -171,46 +149,43 @@ class DeviceRollout:
             self.states[step + 1].copy_(state)
         return self._views[step]
 
-    def _repeat_record(self, ap, at, step, obs, done, stream):
-        """The env's action repeat (sfmi_repeat.h): sf_step_repeat, then the stand-alone sf_record_step on the window's summed
-        reward -- two launches, the same float32 bookkeeping on the same values as sf_step_record's epilogue."""
-        e, P = self.env, self._ptr
-        ticks = e._ticks_buffer()
-        _lib.check(self._L.sf_step_repeat(e._h, ap, at, e.frame_skip, obs, P["r"], done, P["i"], C.c_void_p(ticks.data_ptr()),
-                                          stream))
-        e.last_ticks = ticks
-        _lib.check(self._L.sf_record_step(e.num_envs, P["r"], done, P["rew"][step], P["mask"][step + 1], P["ep"], P["fin"], ap, at,
-                                          P["act"][step], stream))
+    def _record(self, fn, rew, done, ap, at, step, stream):
+        """The trainer's float32 bookkeeping as a launch of its own (sf_record_step on the engine's int reward at `rew`,
+        sf_record_step_f32 on a normalised one): the same arithmetic on the same values as sf_step_record's epilogue."""
+        P = self._ptr
+        _lib.check(fn(self.env.num_envs, rew, done, P["rew"][step], P["mask"][step + 1], P["ep"], P["fin"], ap, at, P["act"][step],
+                      stream))
 
-    def _step_record(self, ap, at, step, stream):
+    def _step_and_record(self, a, ap, at, step, obs, done, dp, stream):
+        """The agent step into `obs` (an address or None) and the done bytes `done` (at `dp`), with the bookkeeping."""
         e, P = self.env, self._ptr
-        if e.frame_skip > 1 and self.num_stack > 1:
-            self._repeat_record(ap, at, step, None, P["d"], stream)
-            if e.default_geometry:
-                _lib.check(self._L.sf_render_shift(e._h, P["obs"][step], P["obs"][step + 1], self.num_stack, P["d"], stream))
-            else:
-                self.observations[step + 1][:, :-1].copy_(self.observations[step][:, 1:])
-                _lib.check(self._L.sf_render_stack(e._h, P["obs"][step + 1], self.num_stack, self.num_stack - 1, P["d"], stream))
-            return
-        if e.frame_skip > 1:
-            self._repeat_record(ap, at, step, P["obs"][step + 1], P["d"], stream)
-            return
-        if self.num_stack > 1:
-            # the step without an observation, then ONE render launch builds observations[step + 1] from
-            # observations[step]: shift by a frame, zero the finished envs, new frame last
-            _lib.check(self._L.sf_step_record(e._h, ap, at, None, P["r"], P["d"], P["i"], P["rew"][step],
-                                              P["mask"][step + 1], P["ep"], P["fin"], P["act"][step], stream))
-            if e.default_geometry:
-                _lib.check(self._L.sf_render_shift(e._h, P["obs"][step], P["obs"][step + 1], self.num_stack, P["d"], stream))
-            else:
-                # the general renderer (another surface geometry) draws into ONE slot: the shift is a copy here, then the new
-                # frame into the last slot with the finished envs' older slots zeroed by the same launch (sf_render_stack)
-                self.observations[step + 1][:, :-1].copy_(self.observations[step][:, 1:])
-                _lib.check(self._L.sf_render_stack(e._h, P["obs"][step + 1], self.num_stack, self.num_stack - 1, P["d"], stream))
-            return
-        # one launch: the step kernel's epilogue does the trainer's bookkeeping (sfmi.h: sf_step_record)
-        _lib.check(self._L.sf_step_record(e._h, ap, at, P["obs"][step + 1], P["r"], P["d"], P["i"], P["rew"][step],
-                                          P["mask"][step + 1], P["ep"], P["fin"], P["act"][step], stream))
+        if e.frame_skip > 1:  # the env's action repeat has no epilogue for the bookkeeping: two launches
+            e._step_into(a, at, (obs, P["r"], dp, P["i"]), self._rew, done, self._info)
+            self._record(self._L.sf_record_step, P["r"], dp, ap, at, step, stream)
+        else:  # one launch: the step kernel's epilogue does the trainer's bookkeeping (sfmi.h: sf_step_record)
+            e._before_step(a)
+            _lib.check(self._L.sf_step_record(e._h, ap, at, obs, P["r"], dp, P["i"], P["rew"][step], P["mask"][step + 1], P["ep"],
+                                              P["fin"], P["act"][step], stream))
+            e._stepped(a, self._rew, done, self._info)
+
+    def _advance_stack(self, step, stream):
+        """observations[step + 1] from observations[step]: shift by a frame, zero the finished envs, new frame last"""
+        e, P = self.env, self._ptr
+        if e.default_geometry:  # ONE render launch does all three
+            _lib.check(self._L.sf_render_shift(e._h, P["obs"][step], P["obs"][step + 1], self.num_stack, P["d"], stream))
+        else:
+            # the general renderer (another surface geometry) draws into ONE slot: the shift is a copy here, then the new
+            # frame into the last slot with the finished envs' older slots zeroed by the same launch (sf_render_stack)
+            self.observations[step + 1][:, :-1].copy_(self.observations[step][:, 1:])
+            _lib.check(self._L.sf_render_stack(e._h, P["obs"][step + 1], self.num_stack, self.num_stack - 1, P["d"], stream))
+
+    def _step_record(self, a, ap, at, step, stream):
+        P = self._ptr
+        if self.num_stack > 1:  # the step without an observation, then the stack
+            self._step_and_record(a, ap, at, step, None, self._done, P["d"], stream)
+            self._advance_stack(step, stream)
+        else:
+            self._step_and_record(a, ap, at, step, P["obs"][step + 1], self._done, P["d"], stream)
 
     @property
     def num_destruction(self):
@@ -236,12 +211,12 @@ class DeviceRollout:
                              "final_value=critic(ro.final_obs())")
         if final_value is not None:
             fv = final_value.detach().reshape(n).float().contiguous()
-            _lib.check(self._L.sf_compute_returns_tl(self.num_steps, n, _p(self.rewards), _p(self.value_preds), _p(self.masks),
-                                                     _p(nv), _p(fv), _p(self.returns), int(bool(use_gae)), float(gamma),
+            _lib.check(self._L.sf_compute_returns_tl(self.num_steps, n, ptr(self.rewards), ptr(self.value_preds), ptr(self.masks),
+                                                     ptr(nv), ptr(fv), ptr(self.returns), int(bool(use_gae)), float(gamma),
                                                      float(tau), self._stream()))
             return
-        _lib.check(self._L.sf_compute_returns(self.num_steps, n, _p(self.rewards), _p(self.value_preds), _p(self.masks),
-                                              _p(nv), _p(self.returns), int(bool(use_gae)), float(gamma), float(tau),
+        _lib.check(self._L.sf_compute_returns(self.num_steps, n, ptr(self.rewards), ptr(self.value_preds), ptr(self.masks),
+                                              ptr(nv), ptr(self.returns), int(bool(use_gae)), float(gamma), float(tau),
                                               self._stream()))
 
     def after_update(self):

@@ -18,6 +18,7 @@ the finished step.
 
 There is no CPU fallback: without a GPU (or without libsfmi.so) construction raises.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -26,7 +27,7 @@ import torch
 from . import _lib
 from .spaces import Box, Discrete
 
-_ACT_TYPES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+_ACT_TYPES = _lib.act_types()
 _NP_FIELD_DTYPES = {(1, 0): np.uint8, (2, 0): np.int16, (4, 0): np.int32, (8, 0): np.int64,
                     (4, 1): np.float32, (8, 1): np.float64}
 _UNSIGNED_FIELDS = {"spawn_cursor", "missile_mask", "shell_mask", "flags"}
@@ -191,22 +192,16 @@ class SFVecEnv:
                     and tuple(obs.shape) == (self.num_envs,) + tuple(self.obs_shape)):
                 raise ValueError("reset_lanes: out must be a contiguous %s tensor %s on %s"
                                  % (self.obs_dtype, (self.num_envs,) + tuple(self.obs_shape), self.device))
-        # _touch() with the episode log following the mask: the other lanes' running sums go on
-        self._fresh = False
-        if self._durations is not None:
-            self._durations.reset()
-        if self._episodes is not None:
-            self._episodes.restart_where(m)
-        if self._rec is not None:
-            self._rec = None
-            raise RuntimeError("reset_lanes() during a recording: a replay file cannot express a manual reset; "
-                               "the recording was dropped")
+        self._touch(restart=m)  # (the episode log follows the mask: the other lanes' running sums go on)
         _lib.check(self._L.sf_reset_lanes(self._h, C.c_void_p(m.data_ptr()), C.c_void_p(obs.data_ptr()), self._stream()))
         return obs
 
     def step_tensors(self, actions, out=None):
         """Device fast path: `actions` is a contiguous uint8/int32/int64 tensor on this device.
-        Returns (obs, reward int32, done uint8, info uint8) tensors; nothing synchronises."""
+        Returns (obs, reward int32, done uint8, info uint8) tensors; nothing synchronises.
+        (_act_type, _outputs and _step_into written out: this is the call bench.py times at one Python call per launch, barely
+        ahead of a 6 us kernel; the helper form measured no slower on an MI355X, but three more Python frames come out of
+        that margin -- profiles/step_paths.md.)"""
         if actions.device != self.device or not actions.is_contiguous() or actions.numel() != self.num_envs:
             raise ValueError("actions must be a contiguous tensor of %d elements on %s" % (self.num_envs, self.device))
         at = _ACT_TYPES.get(actions.dtype)
@@ -248,29 +243,80 @@ class SFVecEnv:
         actions in agent steps.  1 <= repeat <= 255; repeat == 1 is step_tensors.  ValueError on an auto_reset=False batch;
         RuntimeError for repeat > 1 while a duration log is enabled (it follows single ticks) or during a recording (a replay
         file has no field for it)."""
-        if actions.device != self.device or not actions.is_contiguous() or actions.numel() != self.num_envs:
+        at = self._act_type(actions)
+        bufs, ptrs = self._outputs(out)
+        self._step_into(actions, at, ptrs, bufs[1], bufs[2], bufs[3], repeat=int(repeat), ticks_out=ticks_out)
+        return bufs
+
+    def _act_type(self, actions, rows=False):
+        """THE check of an action tensor in front of a launch: contiguous, on this device, [N] (rows: [K, N]), uint8 / int32 /
+        int64.  Returns the C ABI's act type."""
+        if rows:
+            if actions.device != self.device or not actions.is_contiguous() or actions.dim() != 2 \
+                    or actions.shape[1] != self.num_envs:
+                raise ValueError("actions must be a contiguous [K, %d] tensor on %s" % (self.num_envs, self.device))
+        elif actions.device != self.device or not actions.is_contiguous() or actions.numel() != self.num_envs:
             raise ValueError("actions must be a contiguous tensor of %d elements on %s" % (self.num_envs, self.device))
         at = _ACT_TYPES.get(actions.dtype)
         if at is None:
             raise TypeError("actions dtype must be uint8, int32 or int64 (got %s)" % (actions.dtype,))
-        repeat = int(repeat)
-        if repeat != 1:
-            self._no_duration_log("step_repeat()")
-        if self._rec is not None and repeat > 1:
-            raise RuntimeError("step_repeat() during a recording: a replay file has no field for an action repeat")
-        ticks = self._ticks_buffer(ticks_out)
+        return at
+
+    def _outputs(self, out=None):
+        """((obs, reward, done, info), their addresses) of a step: `out`, else the env's own -- reused ones with addresses made
+        once (reuse_buffers), or fresh ones."""
         if out is None and self._bufs is not None and self.reuse_buffers:
-            bufs, ptrs = self._bufs, self._buf_ptrs
+            return self._bufs, self._buf_ptrs
+        bufs = out if out is not None else self._alloc()
+        return bufs, tuple(C.c_void_p(t.data_ptr()) for t in bufs)
+
+    def _step_into(self, actions, at, ptrs, rew, done, info, repeat=None, ticks_out=None):
+        """THE agent step for callers that own their buffers -- step_repeat and every wrapper (FrameStack, DeviceRollout,
+        FrameRollout): checked `actions` of act type `at` (_act_type), `ptrs` the addresses of (obs or None, reward, done,
+        info), the three tensors for the hooks.  repeat None: what the batch was made for -- frame_skip == 1 is sf_step
+        between _before_step and _stepped, frame_skip > 1 the action repeat.  A repeat given (step_repeat) is always
+        sf_step_repeat, which also says the ticks.  No wrapper calls sf_step or sf_step_repeat itself."""
+        if repeat is None and self.frame_skip == 1:
+            self._before_step(actions)
+            _lib.check(self._L.sf_step(self._h, C.c_void_p(actions.data_ptr()), at, ptrs[0], ptrs[1], ptrs[2], ptrs[3],
+                                       self._stream()))
         else:
-            bufs = out if out is not None else self._alloc()
-            ptrs = tuple(C.c_void_p(t.data_ptr()) for t in bufs)
-        if repeat == 1:
-            self._before_step(actions)  # (sf_step itself: a duration log follows it)
-        _lib.check(self._L.sf_step_repeat(self._h, C.c_void_p(actions.data_ptr()), at, repeat, ptrs[0], ptrs[1], ptrs[2], ptrs[3],
-                                          C.c_void_p(ticks.data_ptr()), self._stream()))
-        self.last_ticks = ticks
-        self._stepped(actions, bufs[1], bufs[2], bufs[3])
-        return bufs
+            if repeat is None:
+                repeat = self.frame_skip
+            if repeat != 1:
+                self._no_duration_log("step_repeat()")
+            if self._rec is not None and repeat > 1:
+                raise RuntimeError("step_repeat() during a recording: a replay file has no field for an action repeat")
+            ticks = self._ticks_buffer(ticks_out)
+            if repeat == 1:
+                self._before_step(actions)  # (sf_step itself: a duration log follows it)
+            _lib.check(self._L.sf_step_repeat(self._h, C.c_void_p(actions.data_ptr()), at, repeat, ptrs[0], ptrs[1], ptrs[2],
+                                              ptrs[3], C.c_void_p(ticks.data_ptr()), self._stream()))
+            self.last_ticks = ticks
+        self._stepped(actions, rew, done, info)
+
+    def _rollout_outputs(self, K, want_obs):
+        """(obs [K, N, ...] or None, reward int32, done uint8, info uint8 [K, N]) of a fused launch"""
+        n, dev = self.num_envs, self.device
+        return (torch.empty((K, n) + self.obs_shape, dtype=self.obs_dtype, device=dev) if want_obs else None,
+                torch.empty((K, n), dtype=torch.int32, device=dev), torch.empty((K, n), dtype=torch.uint8, device=dev),
+                torch.empty((K, n), dtype=torch.uint8, device=dev))
+
+    @contextlib.contextmanager
+    def _rollout_events(self, K):
+        """A fused launch stores one row of event masks PER TICK (a.events[step * n_envs + i], sf_kernels.hip): with
+        events enabled it gets a [K, N] buffer of its own for the duration of the launch (`self.rollout_events`);
+        `self.events` holds one tick's row and would be overrun by K - 1 rows."""
+        ev = None
+        if getattr(self, "events", None) is not None:
+            ev = torch.zeros((K, self.num_envs), dtype=torch.int32, device=self.device)
+            _lib.check(self._L.sf_set_event_output(self._h, C.c_void_p(ev.data_ptr())))
+        self.rollout_events = ev
+        try:
+            yield
+        finally:
+            if ev is not None:
+                _lib.check(self._L.sf_set_event_output(self._h, C.c_void_p(self.events.data_ptr())))
 
     def rollout(self, actions, out=None, want_obs=True):
         """K steps whose actions are all known up front, fused into one launch (sfmi.h: sf_rollout).
@@ -278,40 +324,20 @@ class SFVecEnv:
         (obs [K, N, obs_dim] or None, reward int32 [K, N], done uint8 [K, N], info uint8 [K, N]);
         bit-identical to K `step_tensors` calls.  (An image batch with want_obs gets its frames [K, N, h, w] from K step
         launches each followed by its frames -- the fused launch keeps the state in registers --, in the one call.)"""
-        if actions.device != self.device or not actions.is_contiguous() or actions.dim() != 2 \
-                or actions.shape[1] != self.num_envs:
-            raise ValueError("actions must be a contiguous [K, %d] tensor on %s" % (self.num_envs, self.device))
-        at = _ACT_TYPES.get(actions.dtype)
-        if at is None:
-            raise TypeError("actions dtype must be uint8, int32 or int64 (got %s)" % (actions.dtype,))
-        K, n = actions.shape
-        if out is not None:
-            obs, rew, done, info = out
-        else:
-            obs = torch.empty((K, n) + self.obs_shape, dtype=self.obs_dtype, device=self.device) if want_obs else None
-            rew = torch.empty((K, n), dtype=torch.int32, device=self.device)
-            done = torch.empty((K, n), dtype=torch.uint8, device=self.device)
-            info = torch.empty((K, n), dtype=torch.uint8, device=self.device)
+        at = self._act_type(actions, rows=True)
+        K = actions.shape[0]
+        obs, rew, done, info = out if out is not None else self._rollout_outputs(K, want_obs)
         self._no_duration_log("rollout()")
-        ev = self._rollout_events_begin(K)
-        try:
-            _lib.check(self._L.sf_rollout(self._h, C.c_void_p(actions.data_ptr()), at, int(K),
-                                          C.c_void_p(obs.data_ptr()) if obs is not None else None,
-                                          C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
-                                          C.c_void_p(info.data_ptr()), self._stream()))
-        finally:
-            self._rollout_events_end(ev)
-        self._fresh = False
-        if self._episodes is not None:
-            self._episodes.update(rew, done, info, actions)
-        if self._rec is not None:
-            self._rec.add(actions.to(torch.uint8), rew, done, info)
+        with self._rollout_events(K):
+            _lib.check(self._L.sf_rollout(self._h, C.c_void_p(actions.data_ptr()), at, int(K), _lib.ptr(obs), _lib.ptr(rew),
+                                          _lib.ptr(done), _lib.ptr(info), self._stream()))
+        self._stepped(actions, rew, done, info)
         return obs, rew, done, info
 
     # ------------------------------------------------------------------ replay files (spacefortress_amd/replay.py)
     def _before_step(self, actions):
-        """THE hook in FRONT of every single-step launch with given actions -- step_tensors and the wrappers that call the C
-        ABI themselves (FrameStack.step, DeviceRollout.step, SFVecNormalize's fused step): the duration log reads the flags,
+        """THE hook in FRONT of every single-step launch with given actions -- step_tensors, _step_into and the two fused
+        launches of the wrappers (DeviceRollout's sf_step_record, SFVecNormalize's sf_step_normalize): the duration log reads the flags,
         timers and vulnerability the tick's key calls meet (durations.py) before the launch changes them."""
         if self._durations is not None:
             self._durations.before(actions)
@@ -324,8 +350,8 @@ class SFVecEnv:
                                "given actions -- step / step_tensors and the wrappers built on them" % what)
 
     def _stepped(self, actions, rew, done, info):
-        """THE hook behind every launch that steps the batch -- step_tensors / rollout / the *_sampled calls above, and the
-        wrappers that call the C ABI themselves (FrameStack.step, DeviceRollout.step, SFVecNormalize's fused step): the state is
+        """THE hook behind every launch that steps the batch -- step_tensors / _step_into / rollout / the *_sampled calls
+        above, and the two fused launches of the wrappers (sf_step_record, sf_step_normalize): the state is
         no longer the one sf_create left, the duration log appends what the tick pushed (and empties the vectors of an env
         whose episode ended), and a recording gets the actions with the engine's own (unnormalised) reward, done and info of
         the step(s): [N] or [K, N] device tensors, not synchronised.  The episode log (enable_episode_log) follows the same rows."""
@@ -337,18 +363,22 @@ class SFVecEnv:
         if self._rec is not None:
             self._rec.add(actions.to(torch.uint8), rew, done, info)
 
-    def _touch(self):
+    def _touch(self, restart=None):
         """The state is about to change otherwise than by a recorded step: a recording cannot go on, and the duration log starts
         over (its vectors belong to the Games the batch held: reset() makes new ones, set_field / load_state_dict put the batch
         somewhere the log has not followed).  The episode log drops its running sums -- of EVERY lane, also when only some were
-        loaded (load_lanes / copy_lanes) -- and keeps its finished records and the histogram."""
+        loaded (load_lanes / copy_lanes); of the lanes of the mask `restart` when reset_lanes gives one -- and keeps its
+        finished records and the histogram."""
         self._fresh = False
         if self._durations is not None:
             self._durations.reset()
         if self._episodes is not None:
-            self._episodes.restart()
+            self._episodes.restart() if restart is None else self._episodes.restart_where(restart)
         if self._rec is not None:
             self._rec = None
+            if restart is not None:
+                raise RuntimeError("reset_lanes() during a recording: a replay file cannot express a manual reset; "
+                                   "the recording was dropped")
             raise RuntimeError("reset() / set_field() during a recording: a replay file is the game from a NEW batch on; "
                                "the recording was dropped")
 
@@ -380,21 +410,6 @@ class SFVecEnv:
 
         return Replay.load(path)
 
-    def _rollout_events_begin(self, K):
-        """A fused launch stores one row of event masks PER TICK (a.events[step * n_envs + i], sf_kernels.hip): with
-        events enabled it gets a [K, N] buffer of its own for the duration of the launch (`self.rollout_events`);
-        `self.events` holds one tick's row and would be overrun by K - 1 rows."""
-        ev = None
-        if getattr(self, "events", None) is not None:
-            ev = torch.zeros((K, self.num_envs), dtype=torch.int32, device=self.device)
-            _lib.check(self._L.sf_set_event_output(self._h, C.c_void_p(ev.data_ptr())))
-        self.rollout_events = ev
-        return ev
-
-    def _rollout_events_end(self, ev):
-        if ev is not None:
-            _lib.check(self._L.sf_set_event_output(self._h, C.c_void_p(self.events.data_ptr())))
-
     def seed_actions(self, seed, first_lane=0):
         """Restart the on-device action sampler of `step_sampled` at tick 0 (sfmi.h: sf_seed_actions): lane i then plays
         Philox4x32-10(key = seed, counter = (first_lane + i, tick)) scaled to [0, n_actions).  `first_lane` = this shard's
@@ -405,11 +420,7 @@ class SFVecEnv:
         """One step on actions the lanes draw themselves inside the launch (sfmi.h: sf_step_sampled) -- the random-action
         rollout without an action tensor.  Returns (obs, reward, done, info) like `step_tensors`; `actions_out` (uint8 [N]
         on this device, optional) receives what was played."""
-        if out is None and self._bufs is not None and self.reuse_buffers:
-            bufs, ptrs = self._bufs, self._buf_ptrs
-        else:
-            bufs = out if out is not None else self._alloc()
-            ptrs = tuple(C.c_void_p(t.data_ptr()) for t in bufs)
+        bufs, ptrs = self._outputs(out)
         ao = None
         if actions_out is None and (self._rec is not None or self._episodes is not None):  # a recording / the episode log wants to know what was drawn
             actions_out = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
@@ -420,35 +431,19 @@ class SFVecEnv:
             ao = C.c_void_p(actions_out.data_ptr())
         self._no_duration_log("step_sampled()")
         _lib.check(self._L.sf_step_sampled(self._h, ao, ptrs[0], ptrs[1], ptrs[2], ptrs[3], self._stream()))
-        self._fresh = False
-        if self._episodes is not None:
-            self._episodes.update(bufs[1], bufs[2], bufs[3], actions_out)
-        if self._rec is not None:
-            self._rec.add(actions_out, bufs[1], bufs[2], bufs[3])
+        self._stepped(actions_out, bufs[1], bufs[2], bufs[3])
         return bufs
 
     def rollout_sampled(self, n_steps, want_obs=True, want_actions=True):
         """`rollout` on sampled actions: K ticks in one launch.  Returns (obs, reward, done, info, actions uint8 [K, N])."""
         K, n = int(n_steps), self.num_envs
         self._no_duration_log("rollout_sampled()")
-        obs = torch.empty((K, n) + self.obs_shape, dtype=self.obs_dtype, device=self.device) if want_obs else None
-        rew = torch.empty((K, n), dtype=torch.int32, device=self.device)
-        done = torch.empty((K, n), dtype=torch.uint8, device=self.device)
-        info = torch.empty((K, n), dtype=torch.uint8, device=self.device)
+        obs, rew, done, info = self._rollout_outputs(K, want_obs)
         acts = torch.empty((K, n), dtype=torch.uint8, device=self.device) if (want_actions or self._rec is not None or self._episodes is not None) else None
-        ev = self._rollout_events_begin(K)
-        try:
-            _lib.check(self._L.sf_rollout_sampled(self._h, K, C.c_void_p(acts.data_ptr()) if acts is not None else None,
-                                                  C.c_void_p(obs.data_ptr()) if obs is not None else None,
-                                                  C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
-                                                  C.c_void_p(info.data_ptr()), self._stream()))
-        finally:
-            self._rollout_events_end(ev)
-        self._fresh = False
-        if self._episodes is not None:
-            self._episodes.update(rew, done, info, acts)
-        if self._rec is not None:
-            self._rec.add(acts, rew, done, info)
+        with self._rollout_events(K):
+            _lib.check(self._L.sf_rollout_sampled(self._h, K, _lib.ptr(acts), _lib.ptr(obs), _lib.ptr(rew), _lib.ptr(done),
+                                                  _lib.ptr(info), self._stream()))
+        self._stepped(acts, rew, done, info)
         return obs, rew, done, info, acts
 
     def step_async(self, actions):
@@ -519,15 +514,7 @@ class SFVecEnv:
         if alpha is None:
             _lib.check(self._L.sf_set_score_glyphs(self._h, None, None))
             return
-        a = np.ascontiguousarray(alpha, np.uint8)
-        gw, gh, adv, y0 = (int(v) for v in layout)
-        if a.shape != (11, gh, gw):
-            raise ValueError("alpha must be uint8 [11, gh, gw] = [11, %d, %d]" % (gh, gw))
-        g = _lib.ScoreGlyphs(gw, gh, adv, y0)
-        xs = np.broadcast_to(np.asarray(x0, np.int16), (11, 10))
-        for i in range(11):
-            for j in range(10):
-                g.x0[i][j] = int(xs[i, j])
+        g, a = _lib.score_glyphs(alpha, layout, x0)
         _lib.check(self._L.sf_set_score_glyphs(self._h, C.byref(g), a.ctypes.data_as(C.c_void_p)))
 
     def score_glyphs(self):
@@ -577,15 +564,7 @@ class SFVecEnv:
                       1 if grayscale else 0, _lib.VIEW_FORMATS[format])
         keep = None
         if glyphs is not None:
-            a = np.ascontiguousarray(glyphs["alpha"], np.uint8)
-            gw, gh, adv, y0 = (int(x) for x in glyphs["layout"])
-            if a.shape != (11, gh, gw):
-                raise ValueError("alpha must be uint8 [11, gh, gw] = [11, %d, %d]" % (gh, gw))
-            g = _lib.ScoreGlyphs(gw, gh, adv, y0)
-            xs = np.broadcast_to(np.asarray(glyphs["x0"], np.int16), (11, 10))
-            for i in range(11):
-                for j in range(10):
-                    g.x0[i][j] = int(xs[i, j])
+            g, a = _lib.score_glyphs(glyphs["alpha"], glyphs["layout"], glyphs["x0"])
             v.glyphs, v.glyph_alpha, keep = C.pointer(g), a.ctypes.data_as(C.c_void_p), (g, a)
         w, h = C.c_int32(), C.c_int32()
         _lib.check(self._L.sf_view_size(self._h, C.byref(v), C.byref(w), C.byref(h)))  # (the batch's config)
@@ -760,10 +739,6 @@ class SFVecEnv:
             idx = idx.reshape(-1).contiguous()
         return idx, idx.numel(), (_lib.ACT_I32 if idx.dtype == torch.int32 else _lib.ACT_I64)
 
-    @staticmethod
-    def _ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
     def _obs_arg(self, obs):
         if obs is None:
             return None
@@ -784,7 +759,7 @@ class SFVecEnv:
         if idx is None:
             n, itype = self.num_envs, _lib.ACT_I32
         rows = torch.empty((n, _lib.LANE_STATE_BYTES), dtype=torch.uint8, device=self.device)
-        _lib.check(self._L.sf_save_lanes(self._h, self._ptr(idx), itype, n, C.c_void_p(rows.data_ptr()), self._stream()))
+        _lib.check(self._L.sf_save_lanes(self._h, _lib.ptr(idx), itype, n, C.c_void_p(rows.data_ptr()), self._stream()))
         h = self.lane_state_header()
         return LaneStates(rows, self.gametype, int(h[2]), int(h[3]), _lib.LANE_STATE_VERSION,
                           self._L.sf_build_id().decode())
@@ -813,8 +788,8 @@ class SFVecEnv:
             ridx = ridx.to(lidx.dtype)
         optr = self._obs_arg(obs)
         self._touch()
-        _lib.check(self._L.sf_load_lanes(self._h, self._ptr(lidx), itype, n, C.c_void_p(table.data_ptr()), table.shape[0],
-                                         self._ptr(ridx), optr, self._stream()))
+        _lib.check(self._L.sf_load_lanes(self._h, _lib.ptr(lidx), itype, n, C.c_void_p(table.data_ptr()), table.shape[0],
+                                         _lib.ptr(ridx), optr, self._stream()))
         if check:
             self.check_lanes()
 
@@ -833,7 +808,7 @@ class SFVecEnv:
             s = s.to(d.dtype)
         optr = self._obs_arg(obs)
         self._touch()
-        _lib.check(self._L.sf_copy_lanes(self._h, self._ptr(d), src._h, self._ptr(s), itype, n, optr, self._stream()))
+        _lib.check(self._L.sf_copy_lanes(self._h, _lib.ptr(d), src._h, _lib.ptr(s), itype, n, optr, self._stream()))
         if check:
             self.check_lanes()
 

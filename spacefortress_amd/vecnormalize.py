@@ -59,7 +59,7 @@ class SFVecNormalize:
         return _lib.raw_stream(self.device)
 
     def _filter(self, obs, rew):
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        ptr = _lib.ptr
         rew_out = self._rew if rew is not None else None
         _lib.check(self._L.sf_normalize(self._h, ptr(obs) if self.ob else None, ptr(obs) if self.ob else None,
                                         ptr(rew) if self.ret_on else None, ptr(rew_out) if self.ret_on else None,
@@ -76,23 +76,28 @@ class SFVecNormalize:
 
     def step_tensors(self, actions):
         v = self.venv
-        if not (self.ob and self.ret_on) or not hasattr(v, "_alloc") or getattr(v, "frame_skip", 1) > 1:  # (an action repeat: the env's own step)
+        if not (self.ob and self.ret_on) or not hasattr(v, "_alloc"):
             obs, rew, done, info = v.step_tensors(actions)
             obs, rew = self._filter(obs, rew)
             return obs, rew, done, info
-        # the fused path (sfmi.h: sf_step_normalize): the reduction rides on the step kernel
-        if actions.device != v.device or not actions.is_contiguous() or actions.numel() != v.num_envs:
-            raise ValueError("actions must be a contiguous tensor of %d elements on %s" % (v.num_envs, v.device))
-        at = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}.get(actions.dtype)
-        if at is None:
-            raise TypeError("actions dtype must be uint8, int32 or int64 (got %s)" % (actions.dtype,))
-        obs, rew, done, info = v._alloc()
-        p = lambda t: C.c_void_p(t.data_ptr())
-        v._before_step(actions)
-        _lib.check(self._L.sf_step_normalize(v._h, self._h, p(actions), at, p(obs), p(rew), p(done), p(info), p(self._rew),
-                                             0 if self.training else 1, self._stream()))
-        v._stepped(actions, rew, done, info)  # (rew: the engine's int reward; self._rew the normalised one)
+        (obs, rew, done, info), ptrs = v._outputs()
+        self._step_into(actions, v._act_type(actions), obs, ptrs, rew, done, info)
         return obs, self._rew, done, info
+
+    def _step_into(self, actions, at, obs, ptrs, rew, done, info):
+        """SFVecEnv._step_into with VecNormalize(ob=True, ret=True) behind it: the normalised observation into `obs` (at
+        ptrs[0]), the normalised reward into self._rew; `rew` keeps the engine's int reward, which is what the hooks see.
+        Also DeviceRollout's step behind a normaliser."""
+        v = self.venv
+        if v.frame_skip > 1:  # an action repeat is the env's own step, then the stand-alone normaliser on the window's results
+            v._step_into(actions, at, ptrs, rew, done, info)
+            self._filter(obs, rew)
+            return
+        # the fused path (sfmi.h: sf_step_normalize): the reduction rides on the step kernel
+        v._before_step(actions)
+        _lib.check(self._L.sf_step_normalize(v._h, self._h, _lib.ptr(actions), at, ptrs[0], ptrs[1], ptrs[2], ptrs[3],
+                                             _lib.ptr(self._rew), 0 if self.training else 1, self._stream()))
+        v._stepped(actions, rew, done, info)
 
     def step_async(self, actions):
         if torch.is_tensor(actions):
