@@ -53,6 +53,8 @@
 
 #include "sf_drawrec.h"
 #include "sf_lane_dev.h"  // (with sf_internal.h and sf_layout.h)
+#define SF_EVENTS_FN static __device__ __forceinline__
+#include "sf_events.h"
 
 // ---- the build's switches: numeric tunables that name a real quantity, and one instrument (SF_STAMPS) ----
 // Four waves per workgroup share one LDS copy of the cos/sin table (one barrier, early, while the
@@ -1114,8 +1116,8 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
   //      lane busy (random play: 104 missiles per tile = 2 rows instead of 8-9 slot passes).  An entry that hits the
   //      fortress or leaves the area ORs its slot bit into its OWNER lane's event words in LDS; the survivors are
   //      compacted IN PLACE (ballot + prefix count) as the rows go by -- a row is in registers before anything is
-  //      written, and entries only move down.  What a hit or a miss does to the fortress / score is order dependent
-  //      (slot order within an env), so the owners replay their events from the collected masks afterwards.
+  //      written, and entries only move down.  What the hits and misses do to the fortress / score depends only on how
+  //      many of each an env has (sf_events.h), so the owners count the collected masks afterwards: no replay in slot order.
   //      New missiles (fired this tick, SRC/game.cpp:237-238: before the move) are one more row, lane = owner.
   unsigned hit_count = 0;  // missiles that reached the fortress this tick (alive or not)
   {
@@ -1196,31 +1198,26 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
     dr_proj |= (ev_hit >> 24) & 0xFu;  // (draw records: this env's missiles near the score / the bar, sfd::hud_flags_near)
     ev_hit &= L.mmask;             // hit = live & collided
     ev_out &= L.mmask & ~ev_hit;   // out = live & !hit & outside
-    unsigned ev = ev_hit | ev_out;
+    const unsigned ev = ev_hit | ev_out;
     hit_count = __popc(ev_hit);
     L.mmask &= ~ev;
-    // slot order (SRC/game.cpp:355): one event per lane and round, rounds while any lane has one left; the
-    // fortress state machine of :357-399 as selects (a lane without an event in this round has bit == 0)
-    while (__ballot(ev != 0u) != 0ull) {
-      const unsigned bit = ev & (0u - ev);
-      ev &= ~bit;
-      const bool on = bit != 0u, h = (ev_hit & bit) != 0u;
-      const bool hv = h && (L.fl & SF_FL_FORT_ALIVE);        // a hit on a live fortress (:358)
-      const int inc = hv && L.fort_vuln_t >= sfc::vuln_time;  // :359-363
-      const int low = hv && !inc;                             // inside the vulnerability window (:364-384)
-      const int destroy = low && L.vlner >= sfc::vuln_threshold + 1;
-      L.vlner = inc ? L.vlner + 1 : (low ? 0 : L.vlner);
-      S.vlner_incs += inc;
-      S.max_vlner = (inc && L.vlner > S.max_vlner) ? L.vlner : S.max_vlner;
-      L.fl &= destroy ? ~SF_FL_FORT_ALIVE : ~0u;
-      L.fort_death_t = destroy ? 0 : L.fort_death_t;
-      score(destroy ? sfc::Score<SHAPED>::destroy_reward : 0.0f, rew, L);
-      S.destroyed += destroy;
-      S.resets += low && !destroy;
-      L.fort_vuln_t = hv ? 0 : L.fort_vuln_t;
-      const int miss = on && !h;                              // left the game area (:394-398); miss_penalty is 0
-      score(miss ? -sfc::Score<SHAPED>::miss_penalty : 0.0f, rew, L);
-      S.missed += miss;
+    // slot order (SRC/game.cpp:355) does not matter beyond the two counts: the fortress state machine of :357-399 in
+    // closed form (sf_events.h: no loop, no wave-wide test), and the one amount it can score.  A miss only counts:
+    static_assert(sfc::Score<false>::miss_penalty == 0.0f && sfc::Score<true>::miss_penalty == 0.0f,
+                  "sf_missile_events scores no miss (:394-398)");
+    {
+      const SfMissileEvents e = sf_missile_events((int)hit_count, __popc(ev_out), (L.fl & SF_FL_FORT_ALIVE) != 0u, L.fort_vuln_t,
+                                                  L.vlner, sfc::vuln_time, sfc::vuln_threshold, sfc::Score<SHAPED>::destroy_reward);
+      L.vlner = e.vlner;
+      L.fl &= e.fort_alive ? ~0u : ~SF_FL_FORT_ALIVE;
+      L.fort_vuln_t = e.fort_vuln_t;
+      L.fort_death_t = e.fort_death_reset ? 0 : L.fort_death_t;
+      S.vlner_incs += e.incs;
+      S.max_vlner = e.max_vlner > S.max_vlner ? e.max_vlner : S.max_vlner;
+      S.destroyed += e.destroyed;
+      S.resets += e.resets;
+      S.missed += e.missed;
+      score(e.amount, rew, L);
     }
   }
   SF_STAMP(6, false);
