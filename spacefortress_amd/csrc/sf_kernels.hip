@@ -458,14 +458,15 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
   constexpr int kStaged = SPLIT ? SF_LDS_SPLIT_DOUBLES : SF_LDS_DOUBLES;
   constexpr int kTrigPieces = (kStaged / 2 + NT - 1) / NT;
   // (the LDS map above, for BLK envs; a split launch's: the staged block with the atan table inside it, the event words, then
-  //  the hand-over words in front of the staging rows: the new missiles' (x, y) [BLK d2_t] and meta words [BLK], then four
-  //  words per tile: fired, pool done | count, stores done.  sf_launch_step's lds_bytes is this map's end.)
+  //  the hand-over words in front of the staging rows: the new missiles' (x, y) [BLK d2_t] and meta words [BLK], the
+  //  fortress's shots' (ship - fortress) [BLK d2_t] and slot words [BLK], then four words per tile: fired, pool done | count,
+  //  stores done, shot.  sf_launch_step's lds_bytes is this map's end.)
   constexpr int kLdsEv = kStaged;
   constexpr int kLdsAtab = SPLIT ? SF_CONST_ATAB : kLdsEv + BLK, kLdsHand = SPLIT ? kLdsEv + BLK : kLdsAtab + SF_ATAB_DOUBLES,
-                kLdsHandMeta = kLdsHand + 2 * BLK,
-                kLdsHandFlags = kLdsHandMeta + BLK / 2, kLdsStage = SPLIT ? kLdsHandFlags + BLK / 32 : kLdsHand;
+                kLdsHandMeta = kLdsHand + 2 * BLK, kLdsShot = kLdsHandMeta + BLK / 2, kLdsShotSlot = kLdsShot + 2 * BLK,
+                kLdsHandFlags = SPLIT ? kLdsShotSlot + BLK / 2 : kLdsHandMeta + BLK / 2, kLdsStage = SPLIT ? kLdsHandFlags + BLK / 32 : kLdsHand;
   static_assert(kLdsEv == SF_LDS_EV || SPLIT, "the other kernels' map is the one above");
-  static_assert(kStaged % 2 == 0 && kLdsAtab % 2 == 0 && kLdsHand % 2 == 0 && kLdsStage % 2 == 0, "16-byte LDS accesses");
+  static_assert(kStaged % 2 == 0 && kLdsAtab % 2 == 0 && kLdsHand % 2 == 0 && kLdsShot % 2 == 0 && kLdsStage % 2 == 0, "16-byte LDS accesses");
   extern __shared__ double lds[];  // [SF_LDS_DOUBLES] cos/sin table, the event words, then the obs staging rows (SF_LDS_*)
   const unsigned tid_all = threadIdx.x;
   const unsigned tid = SPLIT ? (tid_all & (unsigned)(BLK - 1)) : tid_all;  // the env of the workgroup this thread works for
@@ -523,12 +524,14 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
     // instructions take the same issue slots.  Issue priority for the first wave and a later start for the pool's loads
     // changed nothing measurable; starting them 1 500 cycles later made the games wait; asked for without waiting for the
     // pool's count: nothing either (tools/ab.py, NOTES.md, profiles/r04_split_ab.txt, profiles/closed_switches.md).
-    // The games' wave does not wait for this one: its poll of the `done` word (stamps 16 -> 17 of the instrument build)
-    // takes 280 cycles at the median, 316 at p90 and 276-336 on the ten slowest waves of a launch, which is the price of
-    // the poll itself (one LDS read and its hand-off to the scalar unit) with the word already set.  Doing the tick's
-    // independent tail in front of that poll -- key timers, computeExtra, eleven features of the row -- therefore has
-    // nothing to hide in and measured +0.09 us per launch; the ship's two chunks stored there as well: +-0
-    // (profiles/step_handover_fill.md).
+    // It also fires the fortress's shell: the games' wave keeps the decision (updateFortress) and files the ship's offset
+    // from the fortress and the slot, word `shot`; the sqrt, the two divisions and the shell's two stores happen here, behind
+    // the `done` word, in issue slots the games' wave leaves free (profiles/step_shell_fire.md).
+    // With the word already set, the games' wave's poll of `done` (stamps 16 -> 17 of the instrument build) costs 280
+    // cycles: one LDS read and its hand-off to the scalar unit.  That was all it took while the missile events were replayed
+    // in a loop (profiles/step_handover_fill.md: the tick's independent tail in front of the poll had nothing to hide in,
+    // +0.09 us per launch); since the closed form the two waves reach the hand-over neck and neck
+    // (profiles/step_outcomes.md, profiles/step_shell_fire.md).
     if (tid_all >= (unsigned)BLK) {  // wave-uniform
       // the pool's count rides in every lane's misc chunk: lane 0's word, by a scalar load
       const unsigned n_word = *reinterpret_cast<const __attribute__((address_space(4))) unsigned*>(
@@ -619,7 +622,28 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the event words are in
       if (lane == 0u) hflags[1] = 0x80000000u | wp;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pool's rows are written (the rare purge below re-reads them)
+      // the shell the fortress fires this tick (fireShell, SRC/game.cpp:159-173), BEHIND the `done` word, so that the games
+      // never wait for it: the games' wave decides (updateFortress below) and files (ship - fortress) and the slot per lane,
+      // then sets `shot`, usually long before this poll; the arithmetic -- one sqrt, two fp64 divisions -- and the shell's two
+      // stores are done here.  vel = shellSpeed * d / |d|, pos = fortress + vel: the same operations on the same values in the
+      // same order as the games' wave of the other launches performs them, so the same bits.
+      static_assert(sfl::kGroups[SF_G_shell_vel].chunk * sfl::kTileLanes == 1024 && sfl::kGroups[SF_G_shell_pos].chunk * sfl::kTileLanes == 1024,
+                    "slot stride of the two stores below");
+      unsigned shot;
+      spins = 0u;
+      while ((shot = (unsigned)__builtin_amdgcn_readfirstlane((int)hflags[3])) == 0u && ++spins < kSpinLimit) __builtin_amdgcn_s_sleep(1);
+      if (spins >= kSpinLimit && lane == 0u) atomicAdd(&a.acc[SF_ACC_HANDOVER], 1ull);  // (never seen; see kSpinLimit)
+      asm volatile("" ::: "memory");
+      if (shot == 2u) {
+        const d2_t dd = reinterpret_cast<const d2_t*>(lds + kLdsShot)[tid];
+        const unsigned sl = reinterpret_cast<const unsigned*>(lds + kLdsShotSlot)[tid];  // the slot (< SF_NSLOT), or bit 31: no shot
+        const double nrm = sqrt(dd.x * dd.x + dd.y * dd.y);
+        const double svx = sfc::shell_speed * (dd.x / nrm), svy = sfc::shell_speed * (dd.y / nrm);
+        const unsigned so = !(sl >> 31) ? o.o16 + sl * 1024u : SF_OOB;
+        sf_buf_st128<kStAux>(__builtin_bit_cast(u4_t, (d2_t{svx, svy})), rs, so, SF_GOFF(shell_vel, 0));
+        sf_buf_st128<kStAux>(__builtin_bit_cast(u4_t, (d2_t{kv_fx + svx, kv_fy + svy})), rs, so, SF_GOFF(shell_pos, 0));
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pool's rows and the new shell are written (the rare purge below re-reads the rows)
       if (lane == 0u) hflags[2] = 1u;
       return;
     }
@@ -932,6 +956,7 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
 
   // ---- updateFortress (SRC/game.cpp:194-216)
   int new_s_slot = -1;
+  unsigned new_s_bit = 0u;  // (a split launch: the new shell's bit of the mask, set behind the shells' walk)
   double new_s_vx = 0, new_s_vy = 0;
   bool fort_respawned = false;
   {
@@ -952,7 +977,27 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
       L.fort_last = moved ? fa : L.fort_last;
       L.fort_t = moved ? 0 : L.fort_t;
     }
-    if (ship_up) {
+    if constexpr (SPLIT) {
+      // fireShell (SRC/game.cpp:159-173), the DECISION only, as selects: the slot, the mask bit, the timer, the event.  The
+      // shell's velocity -- one sqrt and two fp64 divisions, some fifty instructions behind an exec-mask branch that a wave
+      // of 64 games takes on nine ticks in ten for a lane or two -- is not needed by anything this wave does in this tick:
+      // the new shell takes no part in the walk below, because it cannot collide (the ship is alive behind updateShip, hence
+      // not inside the small hexagon, hence farther than 34 from the fortress; the shell sits 6 from it; they meet at 13)
+      // and cannot leave the area (tests/test_shell_fire_model.py holds the hexagon's constants to that).  The tile's missile
+      // wave computes and stores it, from (ship - fortress) and the slot filed here, behind the `shot` word (written last;
+      // LDS is in order per wave; 1: nobody fired, 2: somebody did).
+      const int slot = __ffs(~L.smask) - 1;  // (bits 20..31 of the mask are clear: 0..20)
+      const bool lock = ship_up && L.fort_t >= sfc::lock_time && (L.fl & SF_FL_FORT_ALIVE);
+      const bool fire = lock && slot < SF_NSLOT;
+      new_s_slot = fire ? slot : -1;
+      new_s_bit = fire ? 1u << (slot & 31) : 0u;
+      L.fort_t = lock ? 0 : L.fort_t;
+      reinterpret_cast<d2_t*>(lds + kLdsShot)[tid] = d2_t{L.sx - sfc::fort_x, L.sy - sfc::fort_y};
+      reinterpret_cast<unsigned*>(lds + kLdsShotSlot)[tid] = fire ? (unsigned)slot : 0x80000000u;
+      asm volatile("" ::: "memory");
+      const unsigned shot = __ballot(fire) != 0ull ? 2u : 1u;
+      if (lane == 0u) hflags[3] = shot;
+    } else if (ship_up) {
       if (L.fort_t >= sfc::lock_time && (L.fl & SF_FL_FORT_ALIVE)) {
         // fireShell (SRC/game.cpp:159-173): vel = shellSpeed * (cos, sin)(deg2rad(angle_to_ship)).
         // angle_to_ship is the bearing of d = ship - fortress, so (cos, sin) = d / |d|: one sqrt
@@ -1013,7 +1058,7 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
   // wave with the slot in the lane's offset, not a predicated store per slot: every memory instruction of the four
   // waves of a CU goes through the one address unit they share, idle lanes or not.
   static_assert(sfl::kGroups[SF_G_shell_vel].chunk * sfl::kTileLanes == 1024, "slot stride of the row below");
-  if (__ballot(new_s_slot >= 0) != 0ull)
+  if (!SPLIT && __ballot(new_s_slot >= 0) != 0ull)  // (a split launch: the missile wave's store)
     pst16_at(SF_GOFF(shell_vel, 0), new_s_slot >= 0, (unsigned)new_s_slot * 1024u, d2_t{new_s_vx, new_s_vy});
   {
 #pragma unroll
@@ -1025,7 +1070,7 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
 #pragma unroll
       for (int k = 0; k < 1; k++) {
         const int s = g + k;
-        const bool isnew = (s == new_s_slot);
+        const bool isnew = !SPLIT && (s == new_s_slot);
         const double vx = isnew ? new_s_vx : shvx[s], vy = isnew ? new_s_vy : shvy[s];
         nx[k] = (isnew ? kv_fx : shx[s]) + vx;
         ny[k] = (isnew ? kv_fy : shy[s]) + vy;
@@ -1073,7 +1118,7 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
         if (__ballot(live) == 0ull) continue;
         if (live) {
           double x, y, vx, vy;
-          if (s == new_s_slot) {
+          if (!SPLIT && s == new_s_slot) {
             x = sfc::fort_x;
             y = sfc::fort_y;
             vx = new_s_vx;
@@ -1108,6 +1153,7 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
         }
       }
     }
+    if constexpr (SPLIT) L.smask |= new_s_bit;  // the shell fired this tick: in the count and the lane's stores, not in the walk
   }
 
   // ---- updateMissiles (SRC/game.cpp:353-402) over the tile's missile POOL.  The reference walks 20 slots per env; with
@@ -1478,7 +1524,7 @@ hipError_t sf_launch_step(const SfKernelArgs& a, bool autoturn, bool shaped, con
   // (sf_step_kernel's LDS map: the cos/sin table, the event words, the atan table -- a split launch: the staged constants
   //  block, the event words, the hand-over words -- then the observation staging rows)
   size_t lds_bytes = (size_t)(SF_LDS_DOUBLES + blk + SF_ATAB_DOUBLES) * sizeof(double) + (size_t)blk * a.obs_dim * elem;
-  if (split) lds_bytes = (size_t)(SF_LDS_SPLIT_DOUBLES + blk + 2 * blk + blk / 2 + blk / 32) * sizeof(double) + (size_t)blk * a.obs_dim * elem;
+  if (split) lds_bytes = (size_t)(SF_LDS_SPLIT_DOUBLES + blk + 2 * (2 * blk + blk / 2) + blk / 32) * sizeof(double) + (size_t)blk * a.obs_dim * elem;
 #define SF_GO2(AT, SH, FU, OK, XT, BL, FO)                                                                            \
   hipLaunchKernelGGL((sf_step_kernel<AT, SH, FU, OK, XT, BL, FO>), dim3(grid), dim3((BL) > 1000 ? 2 * ((BL) - 1000) : (BL)), lds_bytes, stream, a.state,    \
                      a.consts, actions, a.n_envs, act_type, reward, done, info, a, obs, vec_ok, n_steps)
