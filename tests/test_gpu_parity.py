@@ -14,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+from bearingref import atan2_correctly_rounded as _atan2_correctly_rounded  # (70-digit arithmetic)
 from conftest import GOLDEN, golden_names
 from sfcompare import compare_state, snapshots_to_fields
 
@@ -576,29 +577,6 @@ def test_bearings_a_whisker_off_the_axes(sfa, oracle_mod, gametype):
     assert not compare_state(sd, sn)
     assert obs_close(obs[0], oo, True).all()
     env.close()
-
-
-def _atan2_correctly_rounded(y, x):
-    """atan2(y, x) of two doubles, correctly rounded, by 70-digit arithmetic: the libm value t0 plus
-    atan((y cos t0 - x sin t0) / (x cos t0 + y sin t0)), sin and cos of t0 by their series."""
-    import math
-    from decimal import Decimal, getcontext
-    getcontext().prec = 70
-    t0 = math.atan2(y, x)
-    T = Decimal(t0)
-    s, c, term, k = Decimal(0), Decimal(0), Decimal(1), 0
-    while abs(term) > Decimal(10) ** -68:
-        if k % 2 == 0:
-            c += term if k % 4 == 0 else -term
-        else:
-            s += term if k % 4 == 1 else -term
-        k += 1
-        term = term * T / k
-    Y, X = Decimal(y), Decimal(x)
-    t = (Y * c - X * s) / (X * c + Y * s)
-    theta = T + t - t ** 3 / 3  # (|t| < 1e-15: the next term is below 1e-75)
-    cands = [t0, math.nextafter(t0, math.inf), math.nextafter(t0, -math.inf)]
-    return min(cands, key=lambda v: abs(Decimal(v) - theta))
 
 
 @pytest.mark.parametrize("gametype", ["autoturn", "youturn"])

@@ -23,6 +23,7 @@ import os
 import numpy as np
 import pytest
 
+from bearingref import VDIR_BOUND, close_on_circle_f32
 from sfcompare import compare_state, obs_close, snapshots_to_fields
 from test_gpu_step_reorder import ST_BIG, ST_SHELL, ST_SMALL, _fresh, _fuzz, _missile_table, _n_actions
 
@@ -120,9 +121,12 @@ def _census_lockstep(env, orc, n, T, sampled, base):
             # A drawn THRUST along the fortress's row or column leaves vdir (column 7) within rounding noise of +-180 degrees,
             # one angle with two names: the device's derived bearing and the oracle's second atan2 differ by an ulp of pi
             # there (sf_lane_dev.h: compute_extras) and land on either side, with the parent's library as with this one.
-            # So this run compares every other column, to sfcompare's float32 tolerance; the NOOP runs compare all, bit for bit.
+            # So this run compares every other column to sfcompare's float32 tolerance and column 7 ON THE CIRCLE, by the rule of
+            # tests/bearingref.py: device and oracle are each within VDIR_BOUND of the true angle, so the float32 the device
+            # shows is within twice that, and half a float32 ulp, of the oracle's double, mod 360.  The NOOP runs compare all,
+            # bit for bit.
             ok = obs_close(obs, oo, False)
-            ok[:, 7] = True
+            ok[:, 7] = close_on_circle_f32(obs[:, 7], oo[:, 7], 2 * VDIR_BOUND, 360)
             bad = np.argwhere(~ok)
         else:
             want = oo.astype(np.float32)

@@ -2,9 +2,12 @@
 reference's own file over its own CPython extension; see tests/test_wrapper_golden.py for what is stored and what is masked).
 
 Bar: reward / done / info identical on every step of the 15 runs x 3 observation types; every observation column that is an
-integer, a flag, a position, a velocity or a timer BIT-identical in float64; the three columns that come out of atan2 / sqrt
-chains (aim, vdir, ndist and what normalized-features makes of them) within 1e-9 absolute (the device's libm is not glibc's, and
-vdir's first angle is derived from the bearing instead of a second atan2: DESIGN 9) -- about 84 % of them are bit-identical and
+integer, a flag, a position, a velocity or a timer BIT-identical in float64, and so is ndist (IEEE operations on both sides:
+tests/bearingref.py); the two columns that come out of atan2 chains (aim, vdir and what normalized-features makes of them)
+within TWICE the bound tests/bearingref.py derives from the code's roundings -- 1.88e-13 degrees on aim, 2.18e-13 on vdir: the
+device and the reference's glibc path are each within one bound of the true angle (tests/test_gpu_bearing_columns.py holds
+every path to the 70-digit value itself, on the circle: vdir's first angle is derived from the bearing instead of a second atan2,
+DESIGN 9) -- about 84 % of the three are bit-identical and
 the share is asserted (> 70 %); monitors, thresholds of them, are compared exactly.  Masked: kill_ready, the reference's
 undefined getter (features / normalized-features column 12, monitors column 3).  The reset observation is compared in full with
 SF_FLAG_REF_RESET_OBS (aim = vdir = ndist = 0, as the reference returns on fresh memory) -- for the first Game of every run
@@ -15,6 +18,7 @@ import os
 import numpy as np
 import pytest
 
+import bearingref as br
 from conftest import GOLDEN
 from test_wrapper_golden import EXTRAS, KILL_READY, OBS_TYPES, RUNS, WRAPPER, unmasked
 
@@ -35,14 +39,16 @@ def sfa():
 
 def _check(got, want, ot, what, stats):
     cols = unmasked(ot, want.shape[-1])
-    soft = [c for c in EXTRAS[ot] if c in cols] if ot != "monitors" else []
+    extras = [c for c in EXTRAS[ot] if c in cols] if ot != "monitors" else []
+    soft = [c for c in extras if c in br.RULES[ot]]  # aim and vdir; ndist (column 8) is IEEE arithmetic both sides: exact
     hard = [c for c in cols if c not in soft]
     assert np.array_equal(got[..., hard], want[..., hard]), (what, "exact columns", np.argwhere(got[..., hard] != want[..., hard])[:5].tolist())
-    if soft:
-        d = np.abs(got[..., soft] - want[..., soft])
-        assert d.max() <= 1e-9, (what, "extras", float(d.max()))
-        stats[0] += int((got[..., soft] == want[..., soft]).sum())
-        stats[1] += d.size
+    for c in soft:
+        d = np.abs(got[..., c] - want[..., c])  # (not on the circle: no recorded run has the two on opposite ends of a range)
+        assert d.max() <= 2 * br.RULES[ot][c][0], (what, "column %d" % c, float(d.max()))
+    if extras:
+        stats[0] += int((got[..., extras] == want[..., extras]).sum())
+        stats[1] += got[..., extras].size
 
 
 @pytest.mark.parametrize("name", RUNS)
