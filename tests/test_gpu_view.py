@@ -189,6 +189,50 @@ def test_grey_view_at_the_wrappers_geometry_is_its_image(sfa):
     env.close()
 
 
+def _wrapper_geometries():
+    """(name, (scale, vx, vy, vw, vh, ls), snaps, atlas index of score_glyphs.npz or None): the four geometries of
+    geometries.npz and the close-up of zoom.npz (scale .75, 187 x 195: a wireframe larger than one accumulator window of the
+    rasteriser, arcs 47 pixels out), each with the fixture's states: dead ships, dead fortresses, missiles, shells."""
+    z = np.load(os.path.join(GOLDEN, "frames", "geometries.npz"))
+    out = [("geometry %d" % gi, tuple(float(v) for v in g), z["snaps"], gi + 1) for gi, g in enumerate(z["geometries"])]
+    q = np.load(os.path.join(GOLDEN, "frames", "zoom.npz"))
+    return out + [("close-up", tuple(float(v) for v in q["geometry"]), q["snaps"], None)]
+
+
+def test_grey_view_at_any_wrapper_geometry_is_its_image(sfa):
+    """The general renderer and the view kernel paint with the same code (sf_scene_dev.h); here they see the same states in
+    every other geometry the fixtures have: an image-raw batch in the geometry, the fixture's snapshots in lanes 60 .. of 128
+    (two state tiles), and render_view at the same size, viewport and line width, grey, cut into bands of at most 32 rows, is
+    render("image-raw") byte for byte -- with the geometry's atlas where score_glyphs.npz has one, and with none (both draw the
+    seven-segment fallback); the BGRx form is the grey one in B, G and R with x = 255."""
+    from oracle import render_np as R
+    first = 60
+    for name, (sc, vx, vy, vw, vh, ls), snaps, atlas in _wrapper_geometries():
+        n, vp = len(snaps), (vx, vy, vw, vh)
+        lanes = range(first, first + n)
+        env = sfa.SFVecEnv(128, gametype="youturn", obs_type="image-raw", image_geometry=(sc, vp, ls))
+        h, w = env.obs_shape
+        assert h > 32  # (more than one band)
+        batch = snaps[np.arange(128) % n]
+        batch[first:first + n] = snaps
+        _load(env, batch)
+        for A in ([R.load_glyphs(atlas)] if atlas is not None else []) + [None]:
+            if A is None:
+                env.set_score_glyphs(None)
+            else:
+                env.set_score_glyphs(A["alpha"], A["layout"], A["x0"])
+            assert (env.score_glyphs() is None) == (A is None)
+            what = (name, "atlas" if A is not None else "fallback")
+            want = env.render("image-raw").cpu().numpy()[first:first + n]
+            got = env.render_view(w, h, vp, ls, grayscale=True, format="gray", lanes=lanes, glyphs=env.score_glyphs()).cpu().numpy()
+            assert got.shape == want.shape == (n, h, w)
+            _same(got, want, what)
+            bgrx = env.render_view(w, h, vp, ls, grayscale=True, lanes=lanes, glyphs=env.score_glyphs()).cpu().numpy()
+            _same(bgrx[..., :3], np.repeat(want[..., None], 3, axis=3), what + ("bgrx",))
+            assert (bgrx[..., 3] == 255).all(), what
+        env.close()
+
+
 def test_lane_ranges_and_a_view_changes_nothing(sfa):
     """A sub-range of lanes is the same lanes of the whole batch's frames; a batch that draws views every step keeps the same
     observations and the same state as its twin that never does -- an image batch and a features batch."""
