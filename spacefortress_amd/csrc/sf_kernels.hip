@@ -448,6 +448,11 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
   constexpr bool SPLIT = BLKP > 1000 && !REPEAT;
   constexpr int BLK = REPEAT ? BLKP - 2000 : (SPLIT ? BLKP - 1000 : BLKP);  // envs per workgroup
   constexpr int NT = SPLIT ? 2 * BLK : BLK;        // threads per workgroup
+  // A launch of one tick at the full workgroup size (batches beyond 32 768 envs: 4 or 4 + 4 waves on every CU) stores a chunk
+  // of the lane when its last writer has run -- see the ship's stores below.  Smaller workgroups leave the CU's address
+  // unit no burst to relieve; there the early stores measured level to +0.02 us per launch and the tick ends with
+  // store_lane_buf as before (profiles/step_wave_ends.md).
+  constexpr bool kEarlySt = !FUSED && BLK == SF_BLOCK;
   static_assert(!SPLIT || (!FUSED && OBSK == 1 && !XTRA), "the split launch exists for the plain step of the default observation");
   static_assert(!FOBS || XTRA, "the final-observation output rides on the XTRA instantiations");
   static_assert(!REPEAT || (FUSED && XTRA && !FOBS && BLK == SF_BLOCK), "the action repeat rides on the fused XTRA instantiations (a.final_obs: a run-time test)");
@@ -1209,6 +1214,14 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
       }
     };
     if constexpr (SPLIT) {  // the tile's missile wave did all of that: wait for its word
+      // A launch of one tick (kEarlySt) stores a chunk of the lane when its last writer has run, not with the others at the end, where
+      // the 4 + 4 waves of a CU queue for its one address unit (19 cycles per memory instruction, NOTES.md).  The ship moves
+      // for the last time in updateShip: its two chunks go out here, in the middle of the launch, while that unit has nothing
+      // to do -- and behind the shells' walk, the last consumer of a load: a wait of the compiler's for a load (it does not
+      // see these stores) would be a wait for their acknowledgement too.  A new game rewrites them: see the lane's stores
+      // below.  A/B at 65 536 envs: 5.77 -> 5.63 us per launch in loop launches, 5.78 -> 5.71 in graph launches
+      // (profiles/step_wave_ends.md)
+      if (kEarlySt) store_lane_ship(rs, o, L);
       unsigned dw, spins = 0u;
       SF_STAMP(16, false);
       while (!((dw = (unsigned)__builtin_amdgcn_readfirstlane((int)hflags[1])) >> 31) && ++spins < kSpinLimit) __builtin_amdgcn_s_sleep(1);
@@ -1234,6 +1247,7 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
               *reinterpret_cast<const d2_t*>(&trig[2 * new_m_angle]), new_m_slot >= 0);
     }
     L.mpool = wp;
+    if (kEarlySt && !SPLIT) store_lane_ship(rs, o, L);  // (as the split launch's above: behind the pool rows, the last loads)
     // the owners collect what happened to their missiles (LDS is in order per wave; the fences pin the compiler)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1265,6 +1279,19 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
       S.missed += e.missed;
       score(e.amount, rew, L);
     }
+  }
+  // The score chunk is final here in a launch of one tick (kEarlySt): the tick's last score() is the one above, the vulnerability and
+  // the three counters that ride in the chunk have their last writers behind them (updateShip, the shells, the events),
+  // and `time` only counts the tick.  It goes out in front of the timers and the reward arithmetic, not behind them.  (The
+  // four updates are the ones updateTime and the statistics make below, on a copy: the tick's text stays what it is for the
+  // launches of several ticks, and the compiler computes each once.)
+  if (kEarlySt) {
+    Lane Ls = L;
+    Ls.time += sfc::tick_ms;
+    Ls.c_maxv = (unsigned)S.max_vlner > L.c_maxv ? (unsigned)S.max_vlner : L.c_maxv;
+    Ls.c_small += (unsigned)S.small_hex_deaths;
+    Ls.c_shell += (unsigned)S.shell_deaths;
+    store_lane_score(rs, o, Ls);
   }
   SF_STAMP(6, false);
 
@@ -1382,7 +1409,17 @@ __global__ __launch_bounds__(BLKP > 2000 ? BLKP - 2000 : (BLKP > 1000 ? 2 * (BLK
   SF_STAMP(11, false);
   if constexpr (!REPEAT)
     if (draw_now) SF_DRAW_HEADER(done && a.auto_reset, dr_proj)  // uniform
-  if (!FUSED) store_lane_buf(rs, o, L);
+  if (!FUSED && !kEarlySt) store_lane_buf(rs, o, L);
+  if (kEarlySt) {
+    // the ship's chunks and the score chunk went out above; a new game rewrites them: once per 5 295 ticks the tile stores
+    // them again, behind new_game and -- same wave, same addresses, same kind of store -- in program order behind the first.
+    // The other four chunks hold a timer, the reward byte or a counter the reward feeds: nothing of them is final earlier.
+    if (__ballot(done && a.auto_reset) != 0ull) {
+      store_lane_ship(rs, o, L);
+      store_lane_score(rs, o, L);
+    }
+    store_lane_rest(rs, o, L);
+  }
   SF_STAMP(14, false);
 
   if constexpr (REPEAT) {

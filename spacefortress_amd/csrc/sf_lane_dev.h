@@ -331,31 +331,53 @@ __device__ __forceinline__ void unpack_lane_late(const LaneLate& t, Lane& L) {
 }
 
 // The lane's seven chunks back to the tile, through the wave's descriptor: the chunk offsets ride in the scalar
-// offset, no 64-bit address per store; write-through (SF_SC_AUX).
-__device__ __forceinline__ void store_lane_buf(__amdgpu_buffer_rsrc_t rs, const Off& o, const Lane& L) {
-  constexpr int aux = SF_SC_AUX;
-#define SF_BST16(group, v) \
-  sf_buf_st128<aux>(__builtin_bit_cast(u4_t, v), rs, o.o16, SF_GOFF(group, 0))
-  SF_BST16(ship_pos, (d2_t{L.sx, L.sy}));
+// offset, no 64-bit address per store; write-through (SF_SC_AUX).  Four pieces, so that a launch of one tick can issue a piece
+// as soon as its last writer has run (sf_step_kernel, kEarlySt: the ship behind the shells' walk, the score chunk behind the
+// missile events, the rest behind the timers and the reward); store_lane_buf is the four in the order the chunks always
+// had.  The pieces are macros over (rs, o, L): as functions inside store_lane_buf they gave the launches that keep the one
+// store other instruction orders around it; as text, none (tools/device_code_id.py --kernels, profiles/step_wave_ends.md).
+#define SF_BST16(group, v) sf_buf_st128<SF_SC_AUX>(__builtin_bit_cast(u4_t, v), rs, o.o16, SF_GOFF(group, 0))
+#define SF_ST_LANE_SHIP                    \
+  SF_BST16(ship_pos, (d2_t{L.sx, L.sy})); \
   SF_BST16(ship_vel, (d2_t{L.vx, L.vy}));
-  // the packed words of sf_layout.h (SF_W_*): a value below, a per-episode counter above
-  const unsigned er = (unsigned)L.ep_return;
-  SF_BST16(timers_a, (i4_t{(int)(((unsigned)L.prev_vlner & 0xFFFu) | ((L.c_incs & 0xFFFu) << 12) | (L.c_big << 24)),
-                           (int)(((unsigned)L.fire_t & 0xFFFFu) | (L.c_resets << 16)),
-                           (int)(((unsigned)L.thrust_t & 0xFFFFu) | (L.c_missed << 16)),
-                           (int)(((unsigned)L.left_t & 0xFFFFu) | (er << 16))}));
+// the packed words of sf_layout.h (SF_W_*): a value below, a per-episode counter above (`er`: the episode's return)
+#define SF_ST_LANE_TIMERS                                                                                                       \
+  SF_BST16(timers_a, (i4_t{(int)(((unsigned)L.prev_vlner & 0xFFFu) | ((L.c_incs & 0xFFFu) << 12) | (L.c_big << 24)),           \
+                           (int)(((unsigned)L.fire_t & 0xFFFFu) | (L.c_resets << 16)),                                         \
+                           (int)(((unsigned)L.thrust_t & 0xFFFFu) | (L.c_missed << 16)),                                       \
+                           (int)(((unsigned)L.left_t & 0xFFFFu) | (er << 16))}));                                              \
   SF_BST16(timers_b, (i4_t{(int)(((unsigned)L.right_t & 0xFFFFu) | (er & 0xFFFF0000u)), L.fort_t, L.fort_death_t, L.fort_vuln_t}));
-  SF_BST16(score, (i4_t{__float_as_int(L.points), __float_as_int(L.raw),
-                        (int)(((unsigned)L.vlner & 0xFFFu) | ((L.c_maxv & 0xFFFu) << 12) | (L.c_small << 24)),
+#define SF_ST_LANE_SCORE                                                                                             \
+  SF_BST16(score, (i4_t{__float_as_int(L.points), __float_as_int(L.raw),                                            \
+                        (int)(((unsigned)L.vlner & 0xFFFu) | ((L.c_maxv & 0xFFFu) << 12) | (L.c_small << 24)),      \
                         (int)(((unsigned)L.time & 0xFFFFFFu) | (L.c_shell << 24))}));
-  SF_BST16(misc, (i4_t{L.death_t, (int)((L.cursor & 0xFFFFFFu) | (L.c_destroyed << 24)), (int)(L.mmask | (L.mpool << SF_MPOOL_SHIFT)),
-                       (int)(L.smask | (L.ep_kills << SF_KILLS_SHIFT))}));
-#undef SF_BST16
-  sf_buf_st128<aux>(
-      u4_t{(unsigned)(L.angle & 0xFFFF) | ((unsigned)(L.fort_angle & 0xFFFF) << 16),
-           (unsigned)(L.fort_last & 0xFFFF) | ((L.fl & 0xFFFFu) << 16), L.kc0, L.kc1},
+#define SF_ST_LANE_MISC_SMALL                                                                                                               \
+  SF_BST16(misc, (i4_t{L.death_t, (int)((L.cursor & 0xFFFFFFu) | (L.c_destroyed << 24)), (int)(L.mmask | (L.mpool << SF_MPOOL_SHIFT)),     \
+                       (int)(L.smask | (L.ep_kills << SF_KILLS_SHIFT))}));                                                                 \
+  sf_buf_st128<SF_SC_AUX>(                                                                                                                  \
+      u4_t{(unsigned)(L.angle & 0xFFFF) | ((unsigned)(L.fort_angle & 0xFFFF) << 16),                                                       \
+           (unsigned)(L.fort_last & 0xFFFF) | ((L.fl & 0xFFFFu) << 16), L.kc0, L.kc1},                                                     \
       rs, o.o16, SF_GOFF(small, 0));
+__device__ __forceinline__ void store_lane_buf(__amdgpu_buffer_rsrc_t rs, const Off& o, const Lane& L) {
+  SF_ST_LANE_SHIP
+  const unsigned er = (unsigned)L.ep_return;
+  SF_ST_LANE_TIMERS
+  SF_ST_LANE_SCORE
+  SF_ST_LANE_MISC_SMALL
 }
+__device__ __forceinline__ void store_lane_ship(__amdgpu_buffer_rsrc_t rs, const Off& o, const Lane& L) { SF_ST_LANE_SHIP }
+__device__ __forceinline__ void store_lane_score(__amdgpu_buffer_rsrc_t rs, const Off& o, const Lane& L) { SF_ST_LANE_SCORE }
+// timers_a, timers_b, misc and small: what every tick writes last -- the timers, the reward byte, the counters the reward feeds
+__device__ __forceinline__ void store_lane_rest(__amdgpu_buffer_rsrc_t rs, const Off& o, const Lane& L) {
+  const unsigned er = (unsigned)L.ep_return;
+  SF_ST_LANE_TIMERS
+  SF_ST_LANE_MISC_SMALL
+}
+#undef SF_ST_LANE_SHIP
+#undef SF_ST_LANE_TIMERS
+#undef SF_ST_LANE_SCORE
+#undef SF_ST_LANE_MISC_SMALL
+#undef SF_BST16
 
 __device__ __forceinline__ void store_lane(unsigned char* tb, const Off& o, const Lane& L) {
   store_lane_buf(__builtin_amdgcn_make_buffer_rsrc(tb, 0, (int)sfl::kTileBytes, 0x00020000), o, L);
