@@ -11,7 +11,7 @@ import functools
 
 import numpy as np
 
-from sfcompare import snapshots_to_fields
+from lockstep import fuzz_crowded, load_state
 
 T_RUN = 48
 SENTINEL_BYTE = 0xA5  # trainerref.guarded's
@@ -31,10 +31,9 @@ def oracle_run(gametype, n, obs_type="features", faithful=True, T=T_RUN):
     game's row on done), rew, done, info [T, n], final float64 [T, n, D] (the finished game's last observation at the step it
     finished on, NaN elsewhere), snaps (the oracle's state after the run)."""
     from oracle import oracle as O
-    from test_gpu_parity import _fuzz_base
 
     rng = np.random.default_rng([17, len(gametype), n, len(obs_type), int(faithful)])
-    base, pv = _fuzz_base(O, gametype, n, rng)
+    base, pv = fuzz_crowded(O, gametype, n, rng)
     set_clocks(base, rng, T)
     orc = O.OracleVecEnv(gametype, n, obs_type=obs_type)
     orc.load_snapshots(base, pv)
@@ -80,10 +79,8 @@ def final_rows(run, upto=None):
 
 
 def load_env(env, base, pv):
-    """the constructed start into a device batch (test_gpu_parity._load_both's half)"""
-    for k, v in snapshots_to_fields(base).items():
-        env.set_field(k, v)
-    env.set_field("prev_vlner", np.asarray(pv, np.int32))
+    """the constructed start into a device batch (lockstep.load_both's half)"""
+    load_state(env, base, pv)
 
 
 def make_env(sfa, run, gametype, n, obs_type="features", f64=False, faithful=True, **kw):

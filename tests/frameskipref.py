@@ -10,7 +10,7 @@ The oracle driven ONE ENV AT A TIME through the contract's loop, as a vec-env wo
             final = obs; obs = env.reset(); break
     return obs, total, done, kill, ticks
 
-Start state: test_gpu_parity._fuzz_base, then lane i finishes after 1 + i % 41 more ticks (time = 180000 - 34 f), every 7th
+Start state: lockstep.fuzz_crowded, then lane i finishes after 1 + i % 41 more ticks (time = 180000 - 34 f), every 7th
 lane nowhere near its end (time = 3400).  T = 48 ticks of wall budget, so 48 / K windows.  A run is computed once per argument
 tuple and shared (functools.lru_cache); nobody writes into what it returns.
 """
@@ -26,10 +26,10 @@ KS = (1, 2, 3, 4, 16)
 def start_state(gametype, n, finish=None):
     """-> (base snapshots, prev_vlner, rng).  finish: the ticks lane 0 still plays (n = 1: lane 0 is a 7th lane otherwise)."""
     from oracle import oracle as O
-    from test_gpu_parity import _fuzz_base
+    from lockstep import fuzz_crowded
 
     rng = np.random.default_rng([23, len(gametype), n])
-    base, pv = _fuzz_base(O, gametype, n, rng)
+    base, pv = fuzz_crowded(O, gametype, n, rng)
     f = 1 + np.arange(n) % 41
     base["time"] = 180000 - 34 * f
     base["time"][::7] = 3400

@@ -26,13 +26,13 @@ sf_div_const's documented one), kill_ready as the kernels define it.  Ships that
 
 `pytest -s` prints one table: per case, column and family the largest error in units of its bound (float32: 0 inside the allowed
 interval of floats).  Measured values: profiles/bearing_columns.md."""
-import os
 
 import numpy as np
 import pytest
 
 import bearingref as br
-from sfcompare import compare_state, snapshots_to_fields
+from lockstep import load_state, sfa
+from sfcompare import compare_state
 
 pytestmark = pytest.mark.gpu
 
@@ -40,16 +40,6 @@ torch = pytest.importorskip("torch")
 
 GAMETYPES = ["youturn", "autoturn"]
 INPUTS = ("ship_x", "ship_y", "ship_vx", "ship_vy", "ship_angle")
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 class _World:
@@ -116,9 +106,7 @@ def table():
 def _make(sfa, g, base, **kw):
     n = len(base)
     env = sfa.SFVecEnv(n, gametype=g, **kw)
-    for k, v in snapshots_to_fields(base).items():
-        env.set_field(k, v)
-    env.set_field("prev_vlner", np.zeros(n, np.int32))
+    load_state(env, base, np.zeros(n, np.int32))
     return env
 
 

@@ -8,20 +8,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from lockstep import sfa
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 NAMES = ("thrust_durations", "shot_durations", "shot_intervals_invul", "shot_intervals_vul")
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 @pytest.mark.parametrize("name", ["youturn_hunter", "youturn_rapid_fire", "autoturn_allkeys", "testyouturn_random"])

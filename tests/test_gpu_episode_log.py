@@ -8,19 +8,13 @@ import numpy as np
 import pytest
 
 from eplog_np import RECORD, NpEpisodeLog, make_rows
+from lockstep import sfa
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 FIELDS = ("env", "episode_return", "length", "kills", "fire_actions", "end_row")
 ACT_DTYPES = (np.uint8, np.int32, np.int64, None)
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def _p(t):

@@ -5,17 +5,11 @@ import numpy as np
 import pytest
 
 from framestore_np import gather
+from lockstep import sfa
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 FRAME = 84 * 84
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def _dev_store(frames_np, layout):

@@ -17,22 +17,11 @@ import finalobsref as F
 import frameskipref as R
 import trainerref as TR
 from sfcompare import compare_state, obs_close
+from lockstep import sfa
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import os
-
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def _bytes(t):

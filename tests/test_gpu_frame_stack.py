@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import framestack_np as M
+from lockstep import sfa
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -25,13 +26,6 @@ GEOM = (.25, (130, 80, 450, 460), 3)  # another geometry than the default: the g
 BATCHES = [1, 63, 64, 65, 1000, 4097, 6209]  # a ragged last tile; more than 64 hint words; above SF_PREPASS_MAX_ENVS
 DEPTHS = [1, 2, 3, 4, 5, 16]
 CASES = [(n, s) for n in BATCHES for s in DEPTHS if s < 16 or n <= 1000]
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 @pytest.fixture(scope="module")

@@ -15,20 +15,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from lockstep import load_state, sfa
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -49,9 +40,7 @@ def frames_close(got, want, what):
 
 def _load_snaps(env, snaps, gametype="youturn"):
     """Put reference / oracle snapshots into the lanes of a batch (set_field) -- one snapshot per lane."""
-    from sfcompare import snapshots_to_fields
-    for k, v in snapshots_to_fields(snaps).items():
-        env.set_field(k, v)
+    load_state(env, snaps)
 
 
 @pytest.mark.parametrize("name", ["poses.npz", "scenarios.npz"])
@@ -676,21 +665,21 @@ def test_frames_reproduce_the_recorded_fingerprints(sfa, text, name):
 @pytest.mark.parametrize("gametype,seed", [("youturn", 21), ("autoturn", 22)])
 def test_crowded_constructed_frames_vs_model(sfa, oracle_mod, model, monkeypatch, gametype, seed):
     """Frames play never produces: up to 20 missiles and 20 shells anywhere on (and off) the screen, ships and explosions
-    anywhere, a dead or live fortress at any heading (test_gpu_parity._fuzz_base).  They take the render kernel's rare paths
+    anywhere, a dead or live fortress at any heading (lockstep.fuzz_crowded).  They take the render kernel's rare paths
     -- the twentieth missile's own call, shells in slots 16..19, shells that do and do not fit the free top lanes of the
     missiles' range, several chunks of strokes, a fortress drawn in place under a ship, projectiles over the score and the
     bar (the restart from another background) -- against the numpy model, in both sizes; and with every shortcut switched
     off (drawn in place, env order) the frames must be the same bytes."""
-    from test_gpu_parity import _fuzz_base, _load_both
+    from lockstep import fuzz_crowded, load_both
 
     R, hb, hs, bg = model
     O = oracle_mod
     n = 128
-    base, pv = _fuzz_base(O, gametype, n, np.random.default_rng(seed))
+    base, pv = fuzz_crowded(O, gametype, n, np.random.default_rng(seed))
     # a shell's heading is what its velocity says (set once, at launch: SRC/game.cpp:263); the device keeps the velocity only
     ang = np.degrees(np.arctan2(base["shell_vy"], base["shell_vx"]))
     base["shell_angle"] = np.where(ang < 0, ang + 360.0, ang)
-    env, orc = _load_both(sfa, O, gametype, base, prev_vlner=pv)
+    env, orc = load_both(sfa, O, gametype, base, prev_vlner=pv)
     raw = env.render("image-raw").cpu().numpy()
     small = env.render("image").cpu().numpy()
     snaps = orc.snapshots()
@@ -703,7 +692,7 @@ def test_crowded_constructed_frames_vs_model(sfa, oracle_mod, model, monkeypatch
     env.close()
     monkeypatch.setenv("SFMI_NO_EXPLOSION_CACHE", "1")
     monkeypatch.setenv("SFMI_NO_RENDER_ORDER", "1")
-    plain, _ = _load_both(sfa, O, gametype, base, prev_vlner=pv)
+    plain, _ = load_both(sfa, O, gametype, base, prev_vlner=pv)
     assert np.array_equal(plain.render("image-raw").cpu().numpy(), raw)
     assert np.array_equal(plain.render("image").cpu().numpy(), small)
     plain.close()

@@ -1,26 +1,16 @@
 """Lane states on the device (include/sfmi.h: sf_save_lanes / sf_load_lanes / sf_copy_lanes / sf_check_lanes): a state saved
 from one lane and loaded into another -- another tile, another batch, many lanes at once -- plays on exactly as the original
 does, against the batch itself and against the CPU oracle."""
-import os
 
 import numpy as np
 import pytest
 
 from sfcompare import compare_state, obs_close
 from sfscript import firing_actions, largest_pool, open_loop_actions
+from lockstep import sfa
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def _acts(env, T, rng, policy="hunter"):

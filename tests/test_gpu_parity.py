@@ -16,7 +16,8 @@ import pytest
 
 from bearingref import atan2_correctly_rounded as _atan2_correctly_rounded  # (70-digit arithmetic)
 from conftest import GOLDEN, golden_names
-from sfcompare import compare_state, snapshots_to_fields
+from lockstep import check_ticks, every, fuzz_crowded, load_both, load_state, oracle_ticks, play, run_device, sfa
+from sfcompare import compare_state, obs_close
 
 pytestmark = pytest.mark.gpu
 
@@ -26,40 +27,6 @@ torch = pytest.importorskip("torch")
 def load(name):
     z = np.load(os.path.join(GOLDEN, name + ".npz"))
     return z, json.loads(str(z["meta"]))
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
-
-
-def run_device(env, acts_tn, state_every=None, state_cb=None):
-    """Step `env` through acts_tn [T, N] (uint8) on the device; returns numpy obs/reward/done/info."""
-    T, N = acts_tn.shape
-    dev = env.device
-    a = torch.from_numpy(np.ascontiguousarray(acts_tn)).to(dev)
-    obs = torch.empty((T, N, env.obs_dim), dtype=env.obs_dtype, device=dev)
-    rew = torch.empty((T, N), dtype=torch.int32, device=dev)
-    done = torch.empty((T, N), dtype=torch.uint8, device=dev)
-    info = torch.empty((T, N), dtype=torch.uint8, device=dev)
-    for t in range(T):
-        env.step_tensors(a[t], out=(obs[t], rew[t], done[t], info[t]))
-        if state_every and (t + 1) % state_every == 0:
-            state_cb(t, env.state_dict())
-    torch.cuda.synchronize()
-    env.check_actions()
-    return obs.cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy().astype(bool), info.cpu().numpy().astype(bool)
-
-
-def obs_close(a, b, f64):
-    tol = 1e-9 if f64 else 1e-5
-    scale = np.maximum(1.0, np.abs(b))
-    return np.abs(a.astype(np.float64) - b) <= tol * scale + (0 if f64 else 4e-5)
 
 
 # ------------------------------------------------------------------ golden vectors
@@ -73,21 +40,20 @@ def test_hip_replays_golden(sfa, name):
     env = sfa.SFVecEnv(N, gametype=meta["gametype"], action_set=meta["action_set"], seed=meta["seed"],
                        spawn_skip=meta["spawn_skip"], obs_dtype=torch.float64)
     acts = np.repeat(z["actions"][:, None], N, 1)
-    every = meta["snap_every"]
+    snap_every = meta["snap_every"]
     done_steps = set(np.flatnonzero(z["done"]).tolist())
     problems = []
-
-    def cb(t, sd):
+    # comparing the state each `snap_every` steps costs a sync; thin it out on the long runs
+    stride = snap_every if len(acts) <= 700 else snap_every * max(1, 40 // snap_every)
+    ticks = play(env, acts, "step", every(stride))
+    obs, rew, done, info = ticks.obs, ticks.reward, ticks.done.astype(bool), ticks.info.astype(bool)
+    for t, sd in sorted(ticks.states.items()):
         if t in done_steps:
-            return  # the lane was auto-reset; the golden snapshot is the pre-reset state
-        snaps = np.repeat(z["snaps"][(t + 1) // every - 1][None], N)
+            continue  # the lane was auto-reset; the golden snapshot is the pre-reset state
+        snaps = np.repeat(z["snaps"][(t + 1) // snap_every - 1][None], N)
         bad = compare_state(sd, snaps)
         if bad and len(problems) < 5:
             problems.append((t, bad))
-
-    # comparing the state each `every` steps costs a sync; thin it out on the long runs
-    stride = every if len(acts) <= 700 else every * max(1, 40 // every)
-    obs, rew, done, info = run_device(env, acts, state_every=stride, state_cb=cb)
     assert not problems, problems
     for lane in range(N):
         assert np.array_equal(rew[:, lane], z["reward"]), np.flatnonzero(rew[:, lane] != z["reward"])[:5]
@@ -147,24 +113,21 @@ def lockstep(sfa, oracle_mod, gametype, action_set, obs_type, f64, hunter):
     o0 = env.reset().cpu().numpy()
     oo0 = orc.reset()
     assert obs_close(o0, oo0, f64).all()
-    checkpoints = {}
-
-    def cb(t, sd):
-        checkpoints[t] = sd
-
-    obs, rew, done, info = run_device(env, acts, state_every=250, state_cb=cb)
-    for t in range(T):
-        oo, orw, od, oi = orc.step(acts[t].astype(np.int32))
-        assert np.array_equal(rew[t], orw), (t, np.flatnonzero(rew[t] != orw)[:5])
-        assert np.array_equal(done[t], od) and np.array_equal(info[t], oi), t
-        ok = obs_close(obs[t], oo, f64)
-        assert ok.all(), (t, np.argwhere(~ok)[:5], obs[t][~ok][:5], oo[~ok][:5])
-        if t in checkpoints:
-            bad = compare_state(checkpoints[t], orc.snapshots())
-            assert not bad, (t, bad)
-            assert np.array_equal(checkpoints[t]["prev_vlner"], orc.prev_vlner())
+    ticks = play(env, acts, "step", every(250))
     env.close()
-    return int(info.sum())
+    pvs = {}
+
+    def trace():  # the oracle's ticks, and its prev_vlner at the checkpoints (compare_state does not read that field)
+        for t, tick in enumerate(oracle_ticks(orc, acts, ticks.states.__contains__)):
+            if t in ticks.states:
+                pvs[t] = orc.prev_vlner()
+            yield tick
+
+    check_ticks(ticks, trace(), "close_f64" if f64 else "close_f32")
+    assert sorted(pvs) == sorted(ticks.states)
+    for t, pv in pvs.items():
+        assert np.array_equal(ticks.states[t]["prev_vlner"], pv), t
+    return int(ticks.info.sum())
 
 
 def test_episode_rollover_and_stats(sfa, oracle_mod):
@@ -198,19 +161,6 @@ def test_episode_rollover_and_stats(sfa, oracle_mod):
 
 # ------------------------------------------------------------------ constructed edge cases
 
-def _load_both(sfa, O, gametype, snaps, prev_vlner=None, **kw):
-    n = len(snaps)
-    env = sfa.SFVecEnv(n, gametype=gametype, obs_dtype=torch.float64, **kw)
-    orc = O.OracleVecEnv(gametype, n, **{k: v for k, v in kw.items()
-                                         if k in ("action_set", "obs_type", "spawn_stride", "spawn_skip")})
-    orc.load_snapshots(snaps, prev_vlner)
-    for k, v in snapshots_to_fields(snaps).items():
-        env.set_field(k, v)
-    if prev_vlner is not None:
-        env.set_field("prev_vlner", np.asarray(prev_vlner, np.int32))
-    return env, orc
-
-
 def test_missile_slots_exhausted(sfa, oracle_mod):
     """All 20 missile slots live (unreachable in play): FIRE counts a shot, creates nothing, costs nothing
     (SRC/game.cpp:176-191,239-245).  Also 19 live -> the free slot in the middle is taken."""
@@ -229,7 +179,7 @@ def test_missile_slots_exhausted(sfa, oracle_mod):
     ang = base["missile_angle"].astype(int)
     base["missile_vx"] = tab[ang, 0]
     base["missile_vy"] = tab[ang, 1]
-    env, orc = _load_both(sfa, O, "youturn", base)
+    env, orc = load_both(sfa, O, "youturn", base)
     acts = np.array([[1, 1, 0, 1], [0, 0, 1, 0], [1, 1, 1, 1], [0, 0, 0, 0], [1, 0, 1, 1]], np.uint8)
     obs, rew, done, info = run_device(env, acts)
     for t in range(len(acts)):
@@ -267,7 +217,7 @@ def test_many_shells_and_kill_order(sfa, oracle_mod):
         for s in {0: [1], 1: [2], 2: [0], 3: [19, 0], 4: [1], 5: [3]}[i]:
             base["shell_x"][i, s] = 709.5
             base["shell_vx"][i, s] = 5.0
-    env, orc = _load_both(sfa, O, "youturn", base)
+    env, orc = load_both(sfa, O, "youturn", base)
     acts = np.zeros((3, n), np.uint8)
     obs, rew, done, info = run_device(env, acts)
     for t in range(len(acts)):
@@ -280,98 +230,23 @@ def test_many_shells_and_kill_order(sfa, oracle_mod):
     env.close()
 
 
-def _fuzz_base(O, gametype, n, rng):
-    """Random CONSTRUCTED states (not reachable by play): ships anywhere in the area, arbitrary velocities and timers,
-    up to 20 missiles and 20 shells per lane, fortress dead or alive, any vulnerability.  Returns (snapshots, prev_vlner)."""
-    base = O.OracleVecEnv(gametype, n).snapshots()
-    tab = np.load(os.path.join(GOLDEN, "tables.npz"))["missile_vel_by_angle"]
-    base["ship_alive"] = rng.integers(0, 2, n)
-    base["ship_x"] = np.where(rng.random(n) < 0.5, rng.integers(150, 560, n), rng.uniform(150, 560, n))
-    base["ship_y"] = np.where(rng.random(n) < 0.5, rng.integers(135, 495, n), rng.uniform(135, 495, n))
-    base["ship_vx"] = rng.uniform(-4, 4, n) * (rng.random(n) < 0.9)
-    base["ship_vy"] = rng.uniform(-4, 4, n) * (rng.random(n) < 0.9)
-    base["ship_angle"] = rng.integers(0, 360, n)
-    base["ship_death_timer"] = rng.integers(0, 1200, n)
-    for k in ("fire_timer", "thrust_timer", "left_timer", "right_timer"):
-        base[k] = rng.integers(-50, 50, n)
-    for k in ("fire_flag", "thrust_flag", "left_flag", "right_flag"):
-        base[k] = rng.integers(0, 2, n)
-    if gametype != "youturn" and gametype != "test-youturn":
-        base["left_flag"] = 0
-        base["right_flag"] = 0
-    base["fort_alive"] = rng.random(n) < 0.8
-    base["fort_angle"] = rng.integers(0, 36, n) * 10
-    base["fort_last_angle"] = rng.integers(0, 36, n) * 10
-    base["fort_timer"] = rng.integers(0, 1100, n)
-    base["fort_death_timer"] = rng.integers(0, 1100, n)
-    base["fort_vuln_timer"] = rng.integers(0, 400, n)
-    base["vlner"] = rng.integers(0, 14, n)
-    base["points"] = rng.integers(0, 5, n).astype(np.float32) * np.float32(0.05)
-    base["raw_points"] = base["points"] - np.float32(1.0)
-    base["time"] = rng.integers(0, 5000, n) * 34
-    base["tick"] = base["time"] // 34
-    base["stats"] = rng.integers(0, 50, (n, 13))
-    base["stats"][:, 3] = base["stats"][:, :3].sum(1)  # shipDeaths = bigHex + smallHex + shell deaths (killShip's three call sites); it is not stored
-    nm = rng.integers(0, 21, n)
-    ns = rng.integers(0, 21, n)
-    for i in range(n):
-        ms = rng.choice(20, nm[i], replace=False)
-        base["missile_alive"][i, ms] = 1
-        ss = rng.choice(20, ns[i], replace=False)
-        base["shell_alive"][i, ss] = 1
-    base["missile_x"] = rng.uniform(-10, 720, (n, 20))
-    base["missile_y"] = rng.uniform(-10, 636, (n, 20))
-    near = rng.random((n, 20)) < 0.25  # a quarter of the missiles about to hit the fortress
-    ang = rng.integers(0, 360, (n, 20))
-    base["missile_angle"] = ang
-    base["missile_vx"] = tab[ang, 0]
-    base["missile_vy"] = tab[ang, 1]
-    base["missile_x"] = np.where(near, 355 - tab[ang, 0] + rng.uniform(-25, 25, (n, 20)), base["missile_x"])
-    base["missile_y"] = np.where(near, 315 - tab[ang, 1] + rng.uniform(-25, 25, (n, 20)), base["missile_y"])
-    base["shell_x"] = rng.uniform(-5, 715, (n, 20))
-    base["shell_y"] = rng.uniform(-5, 631, (n, 20))
-    base["shell_vx"] = rng.uniform(-6, 6, (n, 20))
-    base["shell_vy"] = rng.uniform(-6, 6, (n, 20))
-    hit = rng.random((n, 20)) < 0.15  # some shells about to hit the ship
-    base["shell_x"] = np.where(hit, (base["ship_x"] + base["ship_vx"])[:, None] - base["shell_vx"] + rng.uniform(-14, 14, (n, 20)), base["shell_x"])
-    base["shell_y"] = np.where(hit, (base["ship_y"] + base["ship_vy"])[:, None] - base["shell_vy"] + rng.uniform(-14, 14, (n, 20)), base["shell_y"])
-    pv = rng.integers(0, 14, n)
-    return base, pv
-
-
-def _lockstep_from(sfa, O, gametype, base, pv, rng, T, fused=False):
-    n = len(base)
-    env, orc = _load_both(sfa, O, gametype, base, prev_vlner=pv)
-    acts = rng.integers(0, env.n_actions, (T, n)).astype(np.uint8)
-    cps = {}
-    if fused:
-        a = torch.from_numpy(acts).to(env.device)
-        obs, rew, done, info = (x.cpu().numpy() for x in env.rollout(a))
-        done, info = done.astype(bool), info.astype(bool)
-        cps[T - 1] = env.state_dict()
-    else:
-        obs, rew, done, info = run_device(env, acts, state_every=10, state_cb=lambda t, sd: cps.__setitem__(t, sd))
-    n_done = 0
-    for t in range(T):
-        oo, orw, od, oi = orc.step(acts[t].astype(np.int32))
-        assert np.array_equal(rew[t], orw), (t, np.flatnonzero(rew[t] != orw)[:5])
-        assert np.array_equal(done[t], od) and np.array_equal(info[t], oi), t
-        ok = obs_close(obs[t], oo, True)
-        assert ok.all(), (t, np.argwhere(~ok)[:5])
-        n_done += int(od.sum())
-        if t in cps:
-            bad = compare_state(cps[t], orc.snapshots())
-            assert not bad, (t, bad)
+def _play_from(sfa, O, gametype, base, pv, rng, T, fused=False):
+    """Both engines from the state `base`, T random ticks (single steps with the state every ten ticks, or one fused launch
+    with its final state), float64 rows to 1e-9; returns the number of games that ended."""
+    env, orc = load_both(sfa, O, gametype, base, prev_vlner=pv)
+    acts = rng.integers(0, env.n_actions, (T, len(base))).astype(np.uint8)
+    ticks = play(env, acts, "fused", every(T)) if fused else play(env, acts, "step", every(10))
     env.close()
-    return n_done
+    check_ticks(ticks, oracle_ticks(orc, acts, ticks.states.__contains__), "close_f64")
+    return int(ticks.done.sum())
 
 
 @pytest.mark.parametrize("gametype", ["youturn", "autoturn", "test-youturn"])
 def test_fuzzed_states(sfa, oracle_mod, gametype):
     """Constructed states loaded into both engines, then 40 random ticks in lock-step."""
     rng = np.random.default_rng(len(gametype) * 7)
-    base, pv = _fuzz_base(oracle_mod, gametype, 1024, rng)
-    _lockstep_from(sfa, oracle_mod, gametype, base, pv, rng, 40)
+    base, pv = fuzz_crowded(oracle_mod, gametype, 1024, rng)
+    _play_from(sfa, oracle_mod, gametype, base, pv, rng, 40)
 
 
 @pytest.mark.parametrize("gametype,fused", [("youturn", False), ("autoturn", False), ("youturn", True)])
@@ -381,11 +256,11 @@ def test_lanes_of_a_tile_finish_at_different_ticks(sfa, oracle_mod, gametype, fu
     a new game while its neighbours play on must take exactly its entries out of the pool (and nobody else's)."""
     rng = np.random.default_rng(11 + len(gametype) + int(fused))
     n, T = 1024, 48
-    base, pv = _fuzz_base(oracle_mod, gametype, n, rng)
+    base, pv = fuzz_crowded(oracle_mod, gametype, n, rng)
     base["time"] = 180000 - 34 * rng.integers(1, T - 6, n)  # game over (time >= 180000) after 1 .. T-7 more ticks
     base["time"][::7] = 34 * 100                              # ... and some lanes nowhere near it
     base["tick"] = base["time"] // 34
-    n_done = _lockstep_from(sfa, oracle_mod, gametype, base, pv, rng, T, fused=fused)
+    n_done = _play_from(sfa, oracle_mod, gametype, base, pv, rng, T, fused=fused)
     assert n_done >= n - n // 7 - 1
 
 
@@ -469,11 +344,10 @@ def test_fused_rollout_equals_single_steps(sfa, oracle_mod, gametype, obs_type, 
     acts = rng.integers(0, 5 if "you" in gametype else 3, (K, n)).astype(np.uint8)
     envs = []
     for _ in range(2):
-        env, orc = _load_both(sfa, O, gametype, base, obs_type=obs_type, spawn_stride=1)
+        env, orc = load_both(sfa, O, gametype, base, obs_type=obs_type, spawn_stride=1)
         env.close()
         env = sfa.SFVecEnv(n, gametype=gametype, obs_type=obs_type, spawn_stride=1, obs_dtype=dt)
-        for k, v in snapshots_to_fields(base).items():
-            env.set_field(k, v)
+        load_state(env, base)
         envs.append(env)
     single, fused = envs
     obs1, rew1, done1, info1 = run_device(single, acts)
@@ -496,7 +370,7 @@ def test_fused_rollout_equals_single_steps(sfa, oracle_mod, gametype, obs_type, 
             a_, b_ = a_[live_s(s1)], b_[live_s(s2)]
         assert np.array_equal(a_, b_), k
     # and both equal the oracle
-    _, orc = _load_both(sfa, O, gametype, base, obs_type=obs_type, spawn_stride=1)
+    _, orc = load_both(sfa, O, gametype, base, obs_type=obs_type, spawn_stride=1)
     for t in range(K):
         oo, orw, od, oi = orc.step(acts[t].astype(np.int32))
         assert np.array_equal(rew1[t], orw), t
@@ -530,7 +404,7 @@ def test_autoturn_heading_on_the_spawn_lattice(sfa, oracle_mod):
     base["ship_y"] = pts[:, 1]
     base["ship_vx"] = 0.0  # stay on the lattice so the fortress sees integer coordinates too
     base["ship_vy"] = 0.0
-    env, orc = _load_both(sfa, O, "autoturn", base)
+    env, orc = load_both(sfa, O, "autoturn", base)
     acts = np.zeros((1, n), np.uint8)
     obs, rew, done, info = run_device(env, acts)
     oo, orw, od, oi = orc.step(acts[0].astype(np.int32))
@@ -566,7 +440,7 @@ def test_bearings_a_whisker_off_the_axes(sfa, oracle_mod, gametype):
     base["ship_y"] = pts[:, 1]
     base["ship_vx"] = 0.0  # stay where they are
     base["ship_vy"] = 0.0
-    env, orc = _load_both(sfa, O, gametype, base)
+    env, orc = load_both(sfa, O, gametype, base)
     acts = np.zeros((1, n), np.uint8)
     obs, rew, done, info = run_device(env, acts)
     oo, orw, od, oi = orc.step(acts[0].astype(np.int32))
@@ -605,7 +479,7 @@ def test_bearings_on_exact_degree_rays(sfa, oracle_mod, gametype):
     base["ship_y"] = pts[:, 1]
     base["ship_vx"] = 0.0
     base["ship_vy"] = 0.0
-    env, orc = _load_both(sfa, O, gametype, base)
+    env, orc = load_both(sfa, O, gametype, base)
     acts = np.zeros((1, n), np.uint8)
     run_device(env, acts)
     orc.step(acts[0].astype(np.int32))

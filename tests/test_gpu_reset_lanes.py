@@ -5,7 +5,6 @@ alone), against the CPU oracle, against the step kernel's own auto-reset, for fe
 Everything is compared bit for bit.  A batch is brought to a state worth resetting with seeded random actions that fire half
 of the time: the tiles' missile pools then span three and more rows of 64 entries (asserted from get_field where the batch
 has the lanes for it: a tile of fewer than seven lanes cannot hold 129 missiles)."""
-import os
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import pytest
 from eplogref import EpisodeLogModel
 from sfcompare import compare_state, obs_close
 from sfscript import firing_actions as _actions, largest_pool as _largest_pool
+from lockstep import sfa
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -20,16 +20,6 @@ torch = pytest.importorskip("torch")
 SIZES = [1, 63, 64, 65, 129, 4161]
 MASKS = ["none", "all", "one", "ends", "per_tile", "tile", "alternating", "half", "bytes"]
 WARM = 400
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def _make(sfa, n, gametype="youturn", **kw):

@@ -8,17 +8,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from lockstep import sfa
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 TR = os.path.join(GOLDEN, "trainer")
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def _p(t):

@@ -9,12 +9,12 @@ and SURVEY 8(d) counts "action generation on device" into the metric.  What has 
   * the tick counter lives on the device: a captured HIP graph draws NEW actions on every replay;
   * shards seeded with their first lane draw what the one big batch draws.
 """
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from lockstep import sfa
 from sfcompare import compare_state, obs_close
 
 M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -53,16 +53,6 @@ def test_philox_known_answers():
     a = sampled_actions(7, 0, 100000, 0, 4, 5)
     assert a.min() == 0 and a.max() == 4
     assert np.abs(np.bincount(a.ravel(), minlength=5) / a.size - 0.2).max() < 0.005
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 @pytest.mark.gpu

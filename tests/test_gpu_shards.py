@@ -14,22 +14,12 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from sfcompare import compare_state
-from test_gpu_parity import obs_close, run_device
+from lockstep import run_device, sfa
+from sfcompare import compare_state, obs_close
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def test_top_lanes_of_the_metric_batch_continue_the_libc_stream(sfa, oracle_mod):

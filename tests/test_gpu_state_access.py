@@ -11,13 +11,13 @@ Sizes: 1, 63, 64, 65, 255, 256, 257, 321 envs -- 256-thread copy kernels, 64-lan
 partial last tiles of 1, 63 and 1 lanes.  The all-ones and NaN batches are never stepped, drawn or rendered.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import lanerow_np as R
+from lockstep import sfa
 from sfcompare import compare_state
 from sfscript import firing_actions, open_loop_actions
 
@@ -26,16 +26,6 @@ pytestmark = pytest.mark.gpu
 SIZES = [1, 63, 64, 65, 255, 256, 257, 321]
 MISSILE_VIEW = ("missile_x", "missile_y", "missile_angle")
 MISSILE_ALL = ("missile_mask",) + MISSILE_VIEW
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 # ------------------------------------------------------------------ helpers
@@ -495,7 +485,7 @@ def test_one_tick_at_the_edges_of_the_packed_words(sfa, oracle_mod):
     neither (3 mod 4); in every other group of four the word-neighbours -- resets, missed, both halves of ep_return, shell deaths --
     sit at their maxima, else at zero.  One tick on, nothing is flagged and every lane is the oracle's; after the third tick
     the batch is flagged and every lane that was not pushed over still is the oracle's."""
-    from test_gpu_parity import _load_both
+    from lockstep import load_both
 
     O = oracle_mod
     L = O.oracle_lib()
@@ -514,7 +504,7 @@ def test_one_tick_at_the_edges_of_the_packed_words(sfa, oracle_mod):
     base["stats"][maxed, R.ST_MISSED] = 65535
     base["stats"][maxed, R.ST_SHELL] = 255
     base["stats"][:, R.ST_SHIP] = base["stats"][:, :3].sum(1)
-    env, orc = _load_both(sfa, O, "youturn", base, auto_reset=False)
+    env, orc = load_both(sfa, O, "youturn", base, auto_reset=False)
     ep = np.where(maxed, -1, 0).astype(np.int32)
     env.set_field("ep_return", ep)
     noop = torch.zeros(n, dtype=torch.uint8, device=env.device)

@@ -6,25 +6,15 @@ for ONE episode.  What has to hold: as long as every value fits, a batch without
 many episodes' worth of ticks it plays; once one does not, the batch SAYS so (sf_check_state -> OverflowError) instead of
 handing out wrapped numbers; and sf_set_field refuses values a field cannot hold.
 """
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from lockstep import sfa
 from sfcompare import compare_state
 
 STAT_BITS = np.array([8, 8, 8, 10, 16, 8, 16, 16, 16, 16, 16, 12, 12])  # sf_layout.h
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 @pytest.mark.gpu

@@ -18,14 +18,13 @@ and 33 024 envs):
     fortress or leave the area on that tick -- the event words -- and lanes with 19 that fire their 20th -- the hand-over);
     the pool's count, check_state() and the observation rows of the last tile (the staging rows) against the oracle: what
     a shifted LDS map that overlapped would break."""
-import os
-
 import numpy as np
 import pytest
 
 from bearingref import VDIR_BOUND, close_on_circle_f32
-from sfcompare import compare_state, obs_close, snapshots_to_fields
-from test_gpu_step_reorder import ST_BIG, ST_SHELL, ST_SMALL, _fresh, _fuzz, _missile_table, _n_actions
+from lockstep import (ST_BIG, ST_SHELL, ST_SMALL, check_ticks, every, fresh, fuzz_sparse, make_env, missile_table, n_actions, oracle_trace, play,
+                      same_bytes, sfa)
+from sfcompare import compare_state, obs_close
 
 pytestmark = pytest.mark.gpu
 
@@ -38,16 +37,6 @@ BIG = [(174.0, 100.0, 155.0, 315.0), (-0.0, 200.0, 255.0, 141.0), (-174.0, 100.0
        (-173.0, -100.0, 555.0, 315.0), (-0.0, -200.0, 455.0, 488.0), (173.0, -100.0, 255.0, 488.0)]
 SMALL_HEX = [(35.0, 20.0, 315.0, 315.0), (-0.0, 40.0, 335.0, 280.0), (-35.0, 20.0, 375.0, 280.0),
              (-34.0, -20.0, 395.0, 315.0), (-0.0, -40.0, 375.0, 349.0), (34.0, -20.0, 335.0, 349.0)]
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 # ---------------------------------------------------------------- 1. edge census
@@ -75,7 +64,7 @@ def _census_base(O, gametype, n):
     pts = _census_points(quarters=n >= 480)  # (a batch of 256 envs holds the 120 points twice, the larger ones the 240)
     P = len(pts)
     assert 2 * P <= n and P == 2 * 6 * (4 if n >= 480 else 2) * 5
-    base = _fresh(O, gametype, n)
+    base = fresh(O, gametype, n)
     i = np.arange(n)
     tgt = pts[i % P]
     moving = (i // P) % 2 == 1
@@ -93,51 +82,34 @@ def _census_base(O, gametype, n):
     return base, tgt, P
 
 
-def _census_lockstep(env, orc, n, T, sampled, base):
-    """T ticks in lock-step; returns the device's outputs per tick (obs, rew, done, info as numpy)."""
-    outs = []
-    z = torch.zeros(n, dtype=torch.uint8, device=env.device)
-    prev = base
-    for t in range(T):
-        played = np.zeros(n, np.int32)
-        if sampled:
-            ao = torch.empty(n, dtype=torch.uint8, device=env.device)
-            out = env.step_sampled(actions_out=ao)
-            played = ao.cpu().numpy().astype(np.int32)
-        else:
-            out = env.step_tensors(z)
-        obs, rew, done, info = [x.cpu().numpy() for x in out]
-        oo, orw, od, oi = orc.step(played)
-        snaps = orc.snapshots()
-        sd = env.state_dict()
+def _sampled_rule(obs, oo):
+    """A drawn THRUST along the fortress's row or column leaves vdir (column 7) within rounding noise of +-180 degrees, one
+    angle with two names: the device's derived bearing and the oracle's second atan2 differ by an ulp of pi there
+    (sf_lane_dev.h: compute_extras) and land on either side, with the parent's library as with this one.  So the sampled run
+    compares every other column to sfcompare's float32 tolerance and column 7 ON THE CIRCLE, by the rule of
+    tests/bearingref.py: device and oracle are each within VDIR_BOUND of the true angle, so the float32 the device shows is
+    within twice that, and half a float32 ulp, of the oracle's double, mod 360.  The NOOP runs compare all, bit for bit."""
+    ok = obs_close(obs, oo, False)
+    ok[:, 7] = close_on_circle_f32(obs[:, 7], oo[:, 7], 2 * VDIR_BOUND, 360)
+    return ok
+
+
+def _census_lockstep(O, env, gametype, base, pv, T, sampled):
+    """T ticks of NOOP (sampled: of what the lanes draw, which the oracle then plays) against the oracle, the state after
+    every tick; returns (Ticks, the oracle's trace)."""
+    ticks = play(env, np.zeros((T, len(base)), np.uint8), "sampled" if sampled else "step", every(1), check_state=True)
+    trace = oracle_trace(O, gametype, base, pv, ticks.played)
+    for t, (oo, orw, od, oi, snaps) in enumerate(trace):
+        sd, rew = ticks.states[t], ticks.reward[t]
         # what the issue names, every lane, exactly ...
         assert np.array_equal((sd["flags"] & 1) != 0, snaps["ship_alive"] != 0), t
         for st in (ST_BIG, ST_SMALL, ST_SHELL):
             assert np.array_equal(sd["stats"][st], snaps["stats"][:, st]), (t, st)
         assert np.array_equal(rew, orw), (t, np.flatnonzero(rew != orw)[:5])
         assert np.array_equal(sd["ship_death_timer"], snaps["ship_death_timer"]), t
-        # ... and the rest of the tick with it
-        if sampled:
-            # A drawn THRUST along the fortress's row or column leaves vdir (column 7) within rounding noise of +-180 degrees,
-            # one angle with two names: the device's derived bearing and the oracle's second atan2 differ by an ulp of pi
-            # there (sf_lane_dev.h: compute_extras) and land on either side, with the parent's library as with this one.
-            # So this run compares every other column to sfcompare's float32 tolerance and column 7 ON THE CIRCLE, by the rule of
-            # tests/bearingref.py: device and oracle are each within VDIR_BOUND of the true angle, so the float32 the device
-            # shows is within twice that, and half a float32 ulp, of the oracle's double, mod 360.  The NOOP runs compare all,
-            # bit for bit.
-            ok = obs_close(obs, oo, False)
-            ok[:, 7] = close_on_circle_f32(obs[:, 7], oo[:, 7], 2 * VDIR_BOUND, 360)
-            bad = np.argwhere(~ok)
-        else:
-            want = oo.astype(np.float32)
-            bad = np.argwhere(obs.view(np.uint32) != want.view(np.uint32))
-        assert bad.size == 0, (t, bad[:5].tolist(), obs[bad[0][0]].tolist(), oo[bad[0][0]].tolist())
-        assert np.array_equal(done.astype(bool), od) and np.array_equal(info.astype(bool), oi), t
-        bad = compare_state(sd, snaps)
-        assert not bad, (t, bad)
-        outs.append((obs, rew, done, info, sd, snaps, prev))
-        prev = snaps
-    return outs
+    # ... and the rest of the tick with it
+    check_ticks(ticks, trace, _sampled_rule if sampled else "f32_bits")
+    return ticks, trace
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -148,32 +120,20 @@ def test_edge_census(sfa, oracle_mod, gametype, n):
     pv = np.zeros(n, np.int32)
     runs = {}
     for path in ("split", "final_obs", "sampled"):
-        env = sfa.SFVecEnv(n, gametype=gametype)
-        for k, v in snapshots_to_fields(base).items():
-            env.set_field(k, v)
-        env.set_field("prev_vlner", pv)
+        env = make_env(sfa, gametype, base, pv)
         if path == "final_obs":
             env.enable_final_obs()  # (the step leaves the split launch: the XTRA / FOBS instantiation, given actions)
-        orc = O.OracleVecEnv(gametype, n)
-        orc.load_snapshots(base, pv)
-        runs[path] = _census_lockstep(env, orc, n, 2, path == "sampled", base)
-        env.check_actions()
-        env.check_state()
+        runs[path] = _census_lockstep(O, env, gametype, base, pv, 2, path == "sampled")
         env.close()
     # the census is one: ships ON a line live, the ulp to the outside of the big hexagon / the inside of the small one kills
-    s1 = runs["split"][0][5]
+    s1 = runs["split"][1][0][4]
     d = s1["stats"] - base["stats"]
     assert (d[:, ST_BIG] == 1).any() and (d[:, ST_SMALL] == 1).any() and (s1["ship_alive"] == 1).any()
     assert np.array_equal(s1["ship_x"], tgt[:, 0]) and np.array_equal(s1["ship_y"], tgt[:, 1])  # every ship stood on its point
     rest, mov = slice(0, P), slice(P, 2 * P)
     assert np.array_equal(s1["ship_alive"][rest], s1["ship_alive"][mov])  # at rest or arriving: the same verdict
     # the non-split launch with the same (NOOP) actions: the same bits in every output and every state field
-    for t in range(2):
-        a, b = runs["split"][t], runs["final_obs"][t]
-        for x, y in zip(a[:4], b[:4]):
-            assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), t
-        for k in a[4]:
-            assert np.array_equal(np.asarray(a[4][k]).view(np.uint8), np.asarray(b[4][k]).view(np.uint8)), (t, k)
+    same_bytes(runs["split"][0], runs["final_obs"][0])
 
 
 # ---------------------------------------------------------------- 2. path differential
@@ -183,16 +143,13 @@ def test_edge_census(sfa, oracle_mod, gametype, n):
 def test_split_and_non_split_paths_agree_for_300_ticks(sfa, oracle_mod, gametype, n):
     O = oracle_mod
     rng = np.random.default_rng(4100 + n + len(gametype))
-    small, pv_s = _fuzz(O, gametype, 512, rng)
+    small, pv_s = fuzz_sparse(O, gametype, 512, rng)
     idx = np.arange(n) % 512
     base, pv = small[idx].copy(), pv_s[idx]
-    ring = torch.from_numpy(rng.integers(0, _n_actions(gametype), (37, n)).astype(np.uint8))
+    ring = torch.from_numpy(rng.integers(0, n_actions(gametype), (37, n)).astype(np.uint8))
     envs = []
     for non_split in (False, True):
-        env = sfa.SFVecEnv(n, gametype=gametype, seed=7)
-        for k, v in snapshots_to_fields(base).items():
-            env.set_field(k, v)
-        env.set_field("prev_vlner", np.asarray(pv, np.int32))
+        env = make_env(sfa, gametype, base, pv, seed=7)
         if non_split:
             env.enable_final_obs()
         envs.append(env)
@@ -228,8 +185,8 @@ def _full_pool_base(O, gametype, n):
     """The batch's last tile with a full missile pool: 20 missiles in every lane -- slot 0 about to hit the fortress, slot 1
     about to leave the area, the others in flight at headings that run through the table -- but for every fourth lane, which
     has 19 and fires its 20th this tick."""
-    base = _fresh(O, gametype, n)
-    tab = _missile_table()
+    base = fresh(O, gametype, n)
+    tab = missile_table()
     last = np.arange(n - 64, n)
     k = 0
     for i in last:
@@ -259,10 +216,7 @@ def test_full_pool_tick_in_the_last_tile(sfa, oracle_mod, gametype, n):
     O = oracle_mod
     base, last = _full_pool_base(O, gametype, n)
     pv = np.zeros(n, np.int32)
-    env = sfa.SFVecEnv(n, gametype=gametype)
-    for k, v in snapshots_to_fields(base).items():
-        env.set_field(k, v)
-    env.set_field("prev_vlner", pv)
+    env = make_env(sfa, gametype, base, pv)
     orc = O.OracleVecEnv(gametype, 64)
     orc.load_snapshots(base[last], pv[last])
     acts = np.zeros((2, n), np.uint8)

@@ -14,13 +14,11 @@ Shapes: 64 and 256 envs (64 per workgroup: one tile, four), 384 where 360 headin
 workgroup), 32 832 (256), 65 536 (the smallest split launch that takes the staggered start: it runs above 65 280 envs) and
 65 600 (the smallest non-split plain one that does).  The non-split instantiations at 64 and 256 envs through float64
 observations and through step_sampled; a fused rollout of four ticks, which shares the prologue, against four steps."""
-import os
-
 import numpy as np
 import pytest
 
-from sfcompare import compare_state, snapshots_to_fields
-from test_gpu_step_reorder import ST_DESTROYED, ST_INCS, ST_RESETS, ST_SHOTS, _fresh, _fuzz, _missile_table, _n_actions
+from lockstep import (ST_DESTROYED, ST_INCS, ST_RESETS, ST_SHOTS, every, fresh, fused_equals_steps, fuzz_sparse, missile_table, n_actions,
+                      run_lockstep, sfa)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,70 +30,16 @@ MODES = ["split", "f64", "sampled", "fused"]  # float32 step (split launch) | fl
 LOCK, RESPAWN, VULN, TICK = 1000, 1000, 250, 34  # sf_layout.h: lock_time, fort_respawn, vuln_time, tick_ms
 
 
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
-
-
-def _make_env(sfa, gametype, base, pv, mode, extra=None):
-    env = sfa.SFVecEnv(len(base), gametype=gametype, obs_dtype=torch.float64 if mode == "f64" else torch.float32)
-    for k, v in snapshots_to_fields(base).items():
-        env.set_field(k, v)
-    env.set_field("prev_vlner", np.asarray(pv, np.int32))
-    for k, v in (extra or {}).items():
-        env.set_field(k, v)
-    return env
-
-
 def _run(sfa, O, gametype, base, pv, acts, mode="split", lanes=None, extra=None, before=None):
     """Load `base`, play len(acts) ticks (mode "sampled": the lanes draw their own actions, the oracle plays what they drew),
-    compare every tick with the oracle (of `lanes` or of the whole batch).  `before(env)`: called right in front of the first
-    step, for a launch that is to be the second of a pair.  Returns the oracle's trace [(obs, rew, done, info, snapshots)]
-    and the device's final state_dict."""
-    n, T = len(base), len(acts)
-    sel = slice(None) if lanes is None else lanes
-    env = _make_env(sfa, gametype, base, pv, mode, extra)
-    orc = O.OracleVecEnv(gametype, len(base[sel]))
-    orc.load_snapshots(base[sel], np.asarray(pv)[sel])
-    a = torch.from_numpy(np.ascontiguousarray(acts)).to(env.device)
-    if before is not None:
-        before(env)
-    fused = None
-    if mode == "fused":
-        fused = [x.cpu().numpy() for x in env.rollout(a)]
-    trace = []
-    every = 1 if (n <= 512 and mode != "fused") else T
-    for t in range(T):
-        played = acts[t]
-        if mode == "sampled":
-            ao = torch.empty(n, dtype=torch.uint8, device=env.device)
-            out = env.step_sampled(actions_out=ao)
-            played = ao.cpu().numpy()
-        elif mode == "fused":
-            out = None
-        else:
-            out = env.step_tensors(a[t])
-        obs, rew, done, info = [x[t] for x in fused] if mode == "fused" else [x.cpu().numpy() for x in out]
-        oo, orw, od, oi = orc.step(played[sel].astype(np.int32))
-        snaps = orc.snapshots()
-        trace.append((oo, orw, od, oi, snaps))
-        got, want = obs[sel].astype(np.float32), oo.astype(np.float32)
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        assert bad.size == 0, (mode, t, bad[:5].tolist(), got[bad[0][0]].tolist(), want[bad[0][0]].tolist())
-        assert np.array_equal(rew[sel], orw), (mode, t, np.flatnonzero(rew[sel] != orw)[:5])
-        assert np.array_equal(done[sel].astype(bool), od) and np.array_equal(info[sel].astype(bool), oi), (mode, t)
-        if (t + 1) % every == 0:
-            bad = compare_state(env.state_dict(), snaps, lanes=lanes)
-            assert not bad, (mode, t, bad)
-    sd = env.state_dict()
-    env.check_actions()
-    env.close()
-    return trace, sd
+    compare every tick with the oracle (of `lanes` or of the whole batch): rows rounded to float32 as bit patterns; the state
+    after every tick of a batch of up to 512 envs, else (and of a fused launch) after the last.  `before(env)`: called right
+    in front of the first step, for a launch that is to be the second of a pair.  Returns the oracle's trace [(obs, rew,
+    done, info, snapshots)] and the device's final state_dict."""
+    T = len(acts)
+    trace, ticks = run_lockstep(sfa, O, gametype, base, pv, acts, mode, every(1 if (len(base) <= 512 and mode != "fused") else T),
+                                "rounded_f32_bits", lanes=lanes, extra=extra, before=before)
+    return trace, ticks.states[T - 1]
 
 
 # ---------------------------------------------------------------- 1. the words of timers_b, consumed on this tick
@@ -107,8 +51,8 @@ def _setup_timers_b(O, gametype, n):
     press edge and 13 a RIGHT release edge with non-zero right_timer (youturn); 14 a ship that respawns this tick with
     fort_timer running; 15 nothing."""
     rng = np.random.default_rng(700 + n)
-    base = _fresh(O, gametype, n)
-    tab = _missile_table()
+    base = fresh(O, gametype, n)
+    tab = missile_table()
     kind = np.arange(n) % 16
     base["fort_timer"] = 300
     base["fort_timer"][kind < 3] = np.array([LOCK - TICK, LOCK, LOCK + TICK])[kind[kind < 3]]
@@ -197,7 +141,7 @@ def test_thrust_and_fire_at_all_360_headings(sfa, oracle_mod):
     """The cos/sin table's every entry through the ship's thrust and through a missile fired this tick."""
     O = oracle_mod
     n, ang = _setup_headings()
-    base = _fresh(O, "youturn", n)
+    base = fresh(O, "youturn", n)
     base["ship_angle"] = ang
     acts = np.full((2, n), 2, np.uint8)  # THRUST
     acts[0, ::3] = 1                      # FIRE: a missile created this tick at the ship's heading
@@ -214,8 +158,8 @@ def _setup_pool(O, gametype):
     """256 lanes, four tiles whose missile pools hold 0, 40 (one row), 192 (three rows) and 256 entries (a fourth row: the
     dependent-load loop), at headings that run through 0..359."""
     n = 256
-    base = _fresh(O, gametype, n)
-    tab = _missile_table()
+    base = fresh(O, gametype, n)
+    tab = missile_table()
     per_lane = np.concatenate([np.zeros(64, int), (np.arange(64) < 40).astype(int), np.full(64, 3), np.full(64, 4)])
     k = 0
     for i in range(n):
@@ -258,7 +202,7 @@ def test_pool_rows_at_all_headings(sfa, oracle_mod, gametype, mode, second_of_a_
 def _setup_bearings(O, n):
     """Autoturn ships on a grid around the fortress that includes both axes and exact-degree rays (45, 135, ... degrees)."""
     offs = [(dx, dy) for dx in (-100, -80, -60, 0, 60, 80, 100) for dy in (-100, -80, -60, 0, 60, 80, 100) if (dx, dy) != (0, 0)]
-    base = _fresh(O, "autoturn", n)
+    base = fresh(O, "autoturn", n)
     o = np.array(offs)[np.arange(n) % len(offs)]
     base["ship_x"], base["ship_y"] = 355.0 + o[:, 0], 315.0 + o[:, 1]
     return base, o
@@ -301,10 +245,10 @@ def test_three_ticks_at_the_larger_shapes(sfa, oracle_mod, gametype, n):
     oracle, the last tile's among them."""
     O = oracle_mod
     rng = np.random.default_rng(800 + n + len(gametype))
-    small, pv_s = _fuzz(O, gametype, 512, rng)
+    small, pv_s = fuzz_sparse(O, gametype, 512, rng)
     idx = np.arange(n) % 512
     base, pv = small[idx].copy(), pv_s[idx]
-    acts = rng.integers(0, _n_actions(gametype), (3, n)).astype(np.uint8)
+    acts = rng.integers(0, n_actions(gametype), (3, n)).astype(np.uint8)
     lanes = np.sort(np.concatenate([rng.choice(n - 64, 224, replace=False), n - 64 + rng.choice(64, 32, replace=False)]))
     trace, _ = _run(sfa, O, gametype, base, pv, acts, lanes=lanes)
     d = trace[-1][4]["stats"] - base["stats"][lanes]
@@ -322,18 +266,10 @@ def test_fuzzed_states_through_the_other_launches(sfa, oracle_mod, gametype, n, 
     through a fused rollout of K = 4, which must equal four steps -- and the oracle's."""
     O = oracle_mod
     rng = np.random.default_rng(900 + n + len(gametype))
-    base, pv = _fuzz(O, gametype, n, rng)
-    acts = rng.integers(0, _n_actions(gametype), (4, n)).astype(np.uint8)
+    base, pv = fuzz_sparse(O, gametype, n, rng)
+    acts = rng.integers(0, n_actions(gametype), (4, n)).astype(np.uint8)
     trace, _ = _run(sfa, O, gametype, base, pv, acts, mode)
     d = trace[-1][4]["stats"] - base["stats"]
     assert (d[:, ST_RESETS] > 0).any() and (d[:, ST_SHOTS] > 0).any()
     if mode == "fused":  # ... and four single steps give the same arrays as the one fused launch
-        e1 = _make_env(sfa, gametype, base, pv, "fused")
-        e2 = _make_env(sfa, gametype, base, pv, "split")
-        a = torch.from_numpy(acts).to(e1.device)
-        fo = [x.cpu().numpy() for x in e1.rollout(a)]
-        for t in range(4):
-            so = [x.cpu().numpy() for x in e2.step_tensors(a[t])]
-            assert all(np.array_equal(f[t].view(np.uint8), s.view(np.uint8)) for f, s in zip(fo, so)), t
-        e1.close()
-        e2.close()
+        fused_equals_steps(sfa, gametype, base, pv, acts)

@@ -3,7 +3,7 @@ the missile events are counted and resolved in closed form (spacefortress_amd/cs
 tests/test_event_replay_model.py); the shells' outcomes depend on the slot order only through "the lowest colliding slot
 leaves with the ship", which these scenarios hold any walk of the slots to (written with a walk per lane instead of per slot,
 measured and not kept: profiles/step_outcomes.md).  In lock-step with the CPU oracle, through the harness of
-test_gpu_step_reorder.py:
+tests/lockstep.py:
 
   * observation rows as float32 BIT PATTERNS, reward / done / info exactly, the state through sfcompare.compare_state;
   * every scenario asserts, from the ORACLE's trace, that its event happened in the compared tick.
@@ -12,14 +12,11 @@ Shapes: 64 and 256 envs (one tile; four tiles in one workgroup), youturn and aut
 scenarios at 64 envs through a float64-observation batch (the non-split instantiation), step_sampled, and a fused rollout of
 four ticks against four steps; three ticks of constructed states at 16 448, 32 832, 65 536 (128 and 256 envs per workgroup,
 the latter with the staggered start) and 65 600 envs (non-split) on a fixed sample of lanes."""
-import os
-
 import numpy as np
 import pytest
 
-from test_gpu_step_first_burst import _make_env, _run
-from test_gpu_step_reorder import (ST_DEATHS, ST_DESTROYED, ST_INCS, ST_MISSED, ST_RESETS, ST_SHELL, ST_SHOTS, _fresh, _fuzz, _lockstep,
-                                   _missile_table, _n_actions, _oracle_trace)
+from lockstep import (ST_DEATHS, ST_DESTROYED, ST_INCS, ST_MISSED, ST_RESETS, ST_SHELL, ST_SHOTS, every, fresh, fused_equals_steps,
+                      fuzz_sparse, missile_table, n_actions, oracle_trace, run_lockstep, sfa)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,18 +28,8 @@ OTHER = ["f64", "sampled", "fused"]
 T = 4  # ticks: the scenario's tick (every lane plays NOOP), then random play
 
 
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
-
-
 def _acts(rng, gametype, n):
-    acts = rng.integers(0, _n_actions(gametype), (T, n)).astype(np.uint8)
+    acts = rng.integers(0, n_actions(gametype), (T, n)).astype(np.uint8)
     acts[0] = 0
     return acts
 
@@ -68,8 +55,8 @@ def _setup_missile_events(O, gametype, n):
     with a miss between them and a third hit behind; 12 a destroying hit between two misses; 13 nothing; 14 hit, miss, hit,
     miss, hit, miss; 15 one miss."""
     rng = np.random.default_rng(1100 + n + len(gametype))
-    base = _fresh(O, gametype, n)
-    tab = _missile_table()
+    base = fresh(O, gametype, n)
+    tab = missile_table()
     kind = np.arange(n) % 16
 
     def put(i, s, hit):
@@ -140,9 +127,9 @@ def test_missile_events_of_one_tick(sfa, oracle_mod, gametype, n):
     """Up to six events of one env in one tick -- several hits inside and outside the vulnerability window, misses among
     them, a dead fortress -- by split launches."""
     base, pv, acts = _setup_missile_events(oracle_mod, gametype, n)
-    trace = _oracle_trace(oracle_mod, gametype, base, pv, acts)
+    trace = oracle_trace(oracle_mod, gametype, base, pv, acts)
     _events_missile_events(base, trace, n)
-    _lockstep(sfa, gametype, base, pv, acts, trace)
+    run_lockstep(sfa, None, gametype, base, pv, acts, "split", every(1), "f32_bits", trace=trace)
 
 
 # ---------------------------------------------------------------- 2. shells
@@ -157,7 +144,7 @@ def _setup_shells(O, gametype, n, lone=False):
     (slot 4), a higher one leaves the area (12); 11 the lower one leaves, the higher one kills; 12 eight shells, of which slot
     9 kills and slot 14 leaves; 13..15 none.  `lone`: only lane 37 of every tile has shells (slots 0, 6 and 19; 6 kills)."""
     rng = np.random.default_rng(1200 + n + len(gametype) + int(lone))
-    base = _fresh(O, gametype, n)
+    base = fresh(O, gametype, n)
     kind = np.arange(n) % 16
 
     def fly(i, s):  # well inside the area, far from the ship and the fortress' line of fire
@@ -242,9 +229,9 @@ def test_shell_outcomes_of_one_tick(sfa, oracle_mod, gametype, n, lone):
     """Shells in low, high and many slots of a lane, two collisions in one tick, a collision with a dead ship, the new shell
     below a live one, a shell leaving as another kills -- and one lane with shells among 63 without -- by split launches."""
     base, pv, acts = _setup_shells(oracle_mod, gametype, n, lone)
-    trace = _oracle_trace(oracle_mod, gametype, base, pv, acts)
+    trace = oracle_trace(oracle_mod, gametype, base, pv, acts)
     _events_shells(base, trace, n, lone)
-    _lockstep(sfa, gametype, base, pv, acts, trace)
+    run_lockstep(sfa, None, gametype, base, pv, acts, "split", every(1), "f32_bits", trace=trace)
 
 
 # ---------------------------------------------------------------- 3. the same scenarios through the other launches
@@ -258,28 +245,21 @@ def test_the_scenarios_through_the_other_launches(sfa, oracle_mod, gametype, wha
     O, n = oracle_mod, 64
     setup, events = (_setup_missile_events, _events_missile_events) if what == "missiles" else (_setup_shells, _events_shells)
     base, pv, acts = setup(O, gametype, n)
-    trace, _ = _run(sfa, O, gametype, base, pv, acts, mode)
+    # (rows rounded to float32 as bit patterns; the state after every tick, of a fused launch after the last)
+    trace, _ = run_lockstep(sfa, O, gametype, base, pv, acts, mode, every(T if mode == "fused" else 1), "rounded_f32_bits")
     events(base, trace, n)
     if mode == "fused":
-        e1 = _make_env(sfa, gametype, base, pv, "fused")
-        e2 = _make_env(sfa, gametype, base, pv, "split")
-        a = torch.from_numpy(acts).to(e1.device)
-        fo = [x.cpu().numpy() for x in e1.rollout(a)]
-        for t in range(T):
-            so = [x.cpu().numpy() for x in e2.step_tensors(a[t])]
-            assert all(np.array_equal(f[t].view(np.uint8), s.view(np.uint8)) for f, s in zip(fo, so)), t
-        e1.close()
-        e2.close()
+        fused_equals_steps(sfa, gametype, base, pv, acts)
 
 
 # ---------------------------------------------------------------- 4. the larger workgroups
 
 def _setup_large(O, gametype, n):
     rng = np.random.default_rng(1300 + n + len(gametype))
-    small, pv_s = _fuzz(O, gametype, 512, rng)
+    small, pv_s = fuzz_sparse(O, gametype, 512, rng)
     idx = np.arange(n) % 512
     base, pv = small[idx].copy(), pv_s[idx]
-    acts = rng.integers(0, _n_actions(gametype), (3, n)).astype(np.uint8)
+    acts = rng.integers(0, n_actions(gametype), (3, n)).astype(np.uint8)
     lanes = np.sort(np.concatenate([rng.choice(n - 64, 224, replace=False), n - 64 + rng.choice(64, 32, replace=False)]))
     return base, pv, acts, lanes
 
@@ -302,5 +282,5 @@ def test_three_ticks_of_constructed_states_at_the_larger_shapes(sfa, oracle_mod,
     """128 and 256 envs per workgroup, the split launch with the staggered start (65 536) and the smallest non-split plain
     launch (65 600): a seeded sample of 256 lanes against the oracle, the last tile's among them."""
     base, pv, acts, lanes = _setup_large(oracle_mod, gametype, n)
-    trace, _ = _run(sfa, oracle_mod, gametype, base, pv, acts, lanes=lanes)
+    trace, _ = run_lockstep(sfa, oracle_mod, gametype, base, pv, acts, "split", every(len(acts)), "rounded_f32_bits", lanes=lanes)
     _events_large(base, trace, lanes)

@@ -15,6 +15,8 @@ Then the refusals (a duration log or a recording with frame_skip > 1, through ev
 import numpy as np
 import pytest
 
+from lockstep import sfa
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -25,18 +27,6 @@ PATHS = ("step_tensors", "step_repeat", "FrameStack", "DeviceRollout", "DeviceRo
          "FrameRollout", "SFVecNormalize")
 IMAGE_PATHS = ("FrameStack", "DeviceRollout(num_stack)", "FrameRollout")
 CASES = [(1, "ends"), (1, "recording"), (3, "ends")]
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import os
-
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def _n(path):

@@ -20,146 +20,34 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
-from sfcompare import compare_state, snapshots_to_fields
+from lockstep import (ST_BIG, ST_DESTROYED, ST_INCS, ST_MISSED, ST_RESETS, ST_SHELL, ST_SHOTS, ST_SMALL, every, fresh, fuzz_sparse,
+                      missile_table, n_actions, oracle_trace, run_lockstep, sfa)
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-# the oracle's statistics columns (SRC/game.hh:29-43)
-ST_BIG, ST_SMALL, ST_SHELL, ST_DEATHS, ST_RESETS, ST_DESTROYED, ST_MISSED, ST_SHOTS = 0, 1, 2, 3, 4, 5, 6, 7
-ST_INCS = 11
 GAMETYPES = ["youturn", "autoturn"]
 SMALL = [64, 256]
 
 
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
-
-
-def _n_actions(gametype):
-    return 5 if gametype == "youturn" else 3  # action set 1: NOOP, FIRE, THRUST (, LEFT, RIGHT)
-
-
-def _missile_table():
-    return np.load(os.path.join(GOLDEN, "tables.npz"))["missile_vel_by_angle"]
-
-
-def _fresh(O, gametype, n):
-    """n new games, every ship parked where nothing happens to it by itself: inside the big hexagon, outside the small one."""
-    base = O.OracleVecEnv(gametype, n).snapshots()
-    base["ship_x"], base["ship_y"] = 455.0, 315.0
-    base["ship_vx"], base["ship_vy"] = 0.0, 0.0
-    return base
-
-
-def _fuzz(O, gametype, n, rng):
-    """Constructed states, not reachable by play (as test_gpu_parity._fuzz_base, with fewer projectiles so that a tile's
-    pool stays within its first rows and the fortress lives long enough to be hit)."""
-    base = O.OracleVecEnv(gametype, n).snapshots()
-    tab = _missile_table()
-    base["ship_alive"] = rng.random(n) < 0.8
-    base["ship_x"] = np.where(rng.random(n) < 0.5, rng.integers(150, 560, n), rng.uniform(150, 560, n))
-    base["ship_y"] = np.where(rng.random(n) < 0.5, rng.integers(135, 495, n), rng.uniform(135, 495, n))
-    base["ship_vx"] = rng.uniform(-4, 4, n) * (rng.random(n) < 0.9)
-    base["ship_vy"] = rng.uniform(-4, 4, n) * (rng.random(n) < 0.9)
-    base["ship_angle"] = rng.integers(0, 360, n)
-    base["ship_death_timer"] = rng.integers(0, 1200, n)
-    for k in ("fire_timer", "thrust_timer", "left_timer", "right_timer"):
-        base[k] = rng.integers(-50, 50, n)
-    for k in ("fire_flag", "thrust_flag", "left_flag", "right_flag"):
-        base[k] = rng.integers(0, 2, n)
-    if gametype != "youturn":
-        base["left_flag"] = 0
-        base["right_flag"] = 0
-    base["fort_alive"] = rng.random(n) < 0.8
-    base["fort_angle"] = rng.integers(0, 36, n) * 10
-    base["fort_last_angle"] = rng.integers(0, 36, n) * 10
-    base["fort_timer"] = rng.integers(0, 1100, n)
-    base["fort_death_timer"] = rng.integers(0, 1100, n)
-    base["fort_vuln_timer"] = rng.integers(0, 400, n)
-    base["vlner"] = rng.integers(0, 14, n)
-    base["points"] = rng.integers(0, 5, n).astype(np.float32) * np.float32(0.05)
-    base["raw_points"] = base["points"] - np.float32(1.0)
-    base["time"] = rng.integers(0, 5000, n) * 34
-    base["tick"] = base["time"] // 34
-    base["stats"] = rng.integers(0, 50, (n, 13))
-    base["stats"][:, ST_DEATHS] = base["stats"][:, :3].sum(1)  # shipDeaths is the sum of killShip's three call sites
-    for i in range(n):
-        base["missile_alive"][i, rng.choice(20, rng.integers(0, 6), replace=False)] = 1
-        base["shell_alive"][i, rng.choice(20, rng.integers(0, 9), replace=False)] = 1
-    ang = rng.integers(0, 360, (n, 20))
-    near = rng.random((n, 20)) < 0.3  # missiles about to hit the fortress
-    base["missile_angle"] = ang
-    base["missile_vx"] = tab[ang, 0]
-    base["missile_vy"] = tab[ang, 1]
-    base["missile_x"] = np.where(near, 355 - tab[ang, 0] + rng.uniform(-25, 25, (n, 20)), rng.uniform(-10, 720, (n, 20)))
-    base["missile_y"] = np.where(near, 315 - tab[ang, 1] + rng.uniform(-25, 25, (n, 20)), rng.uniform(-10, 636, (n, 20)))
-    base["shell_vx"] = rng.uniform(-6, 6, (n, 20))
-    base["shell_vy"] = rng.uniform(-6, 6, (n, 20))
-    hit = rng.random((n, 20)) < 0.15  # shells about to hit the ship
-    base["shell_x"] = np.where(hit, (base["ship_x"] + base["ship_vx"])[:, None] - base["shell_vx"] + rng.uniform(-14, 14, (n, 20)),
-                               rng.uniform(-5, 715, (n, 20)))
-    base["shell_y"] = np.where(hit, (base["ship_y"] + base["ship_vy"])[:, None] - base["shell_vy"] + rng.uniform(-14, 14, (n, 20)),
-                               rng.uniform(-5, 631, (n, 20)))
-    return base, rng.integers(0, 14, n)
-
-
-def _oracle_trace(O, gametype, base, pv, acts, real_shell_count=False):
-    """The oracle's side of a lock-step: per tick (obs float64, reward, done, info, snapshots after the tick)."""
-    orc = O.OracleVecEnv(gametype, len(base))
-    if real_shell_count:
-        for i in range(len(base)):
-            orc.L.sfo_env_set_faithful_bugs(orc.L.sfo_vec_env_at(orc.h, i), 0)
-    orc.load_snapshots(base, pv)
-    out = []
-    for t in range(len(acts)):
-        out.append(orc.step(acts[t].astype(np.int32)) + (orc.snapshots(),))
-    return out
-
-
 def _lockstep(sfa, gametype, base, pv, acts, trace, real_shell_count=False, lanes=None):
     """Load `base` into a float32 features batch (what split launches serve), play `acts`, compare every tick with `trace`
-    (the oracle's, of `lanes` of the batch or of all of it)."""
-    n = len(base)
-    env = sfa.SFVecEnv(n, gametype=gametype, faithful_bugs=not real_shell_count)
-    for k, v in snapshots_to_fields(base).items():
-        env.set_field(k, v)
-    env.set_field("prev_vlner", np.asarray(pv, np.int32))
-    sel = slice(None) if lanes is None else lanes
-    a = torch.from_numpy(np.ascontiguousarray(acts)).to(env.device)
-    every = 1 if n <= 256 else len(acts)  # (small batches: the state after every tick)
-    for t in range(len(acts)):
-        obs, rew, done, info = (x.cpu().numpy() for x in env.step_tensors(a[t]))
-        oo, orw, od, oi, snaps = trace[t]
-        want = oo.astype(np.float32)
-        bad = np.argwhere(obs[sel].view(np.uint32) != want.view(np.uint32))
-        assert bad.size == 0, (t, bad[:5].tolist(), obs[sel][bad[0][0]].tolist(), want[bad[0][0]].tolist())
-        assert np.array_equal(rew[sel], orw), (t, np.flatnonzero(rew[sel] != orw)[:5])
-        assert np.array_equal(done[sel].astype(bool), od) and np.array_equal(info[sel].astype(bool), oi), t
-        if (t + 1) % every == 0:
-            bad = compare_state(env.state_dict(), snaps, lanes=lanes)
-            assert not bad, (t, bad)
-    env.check_actions()
-    env.close()
+    (the oracle's, of `lanes` of the batch or of all of it): rows as float32 bit patterns; small batches: the state after
+    every tick, the others after the last."""
+    run_lockstep(sfa, None, gametype, base, pv, acts, "split", every(1 if len(base) <= 256 else len(acts)), "f32_bits", lanes=lanes,
+                 trace=trace, faithful_bugs=not real_shell_count)
 
 
 # ---------------------------------------------------------------- 1. lanes of one tile finishing on different ticks
 
 def _setup_finish(O, gametype, n, together):
     rng = np.random.default_rng(100 + n + len(gametype) + int(together))
-    base, pv = _fuzz(O, gametype, n, rng)
+    base, pv = fuzz_sparse(O, gametype, n, rng)
     left = np.array([2, 3, 5, 400])[np.arange(n) % 4] if not together else np.full(n, 2)  # ticks to game over
     base["time"] = 180000 - 34 * left
     base["tick"] = base["time"] // 34
-    return base, pv, rng.integers(0, _n_actions(gametype), (7, n)).astype(np.uint8)
+    return base, pv, rng.integers(0, n_actions(gametype), (7, n)).astype(np.uint8)
 
 
 def _events_finish(trace, n, together):
@@ -180,7 +68,7 @@ def test_new_games_inside_a_tile(sfa, oracle_mod, gametype, n, together):
     """Ticks t, t + 1 and t + 3 each end some lanes of a tile but not all (then: the whole tile in one tick).  The new games'
     rows and ship chunks are the oracle's, the neighbours' rows untouched."""
     base, pv, acts = _setup_finish(oracle_mod, gametype, n, together)
-    trace = _oracle_trace(oracle_mod, gametype, base, pv, acts)
+    trace = oracle_trace(oracle_mod, gametype, base, pv, acts)
     _events_finish(trace, n, together)
     _lockstep(sfa, gametype, base, pv, acts, trace)
 
@@ -191,7 +79,7 @@ def _setup_ship(O, gametype, n):
     """Lane i % 8: 0 a shell kills the ship, 1 the big hexagon, 2 the small hexagon, 3 a dead ship respawns, 4 a shell kills
     it while another leaves the area, 5 a shell passes a DEAD ship, 6 and 7 fly on."""
     rng = np.random.default_rng(200 + n)
-    base = _fresh(O, gametype, n)
+    base = fresh(O, gametype, n)
     kind = np.arange(n) % 8
     for i in range(n):
         k = kind[i]
@@ -218,7 +106,7 @@ def _setup_ship(O, gametype, n):
             base["ship_alive"][i] = 0
             base["ship_death_timer"][i] = 1000 + 34 * int(rng.integers(0, 3))
     acts = np.zeros((3, n), np.uint8)  # nobody thrusts: the ships move as set up
-    acts[:, kind >= 6] = rng.integers(0, _n_actions(gametype), (3, int((kind >= 6).sum())))
+    acts[:, kind >= 6] = rng.integers(0, n_actions(gametype), (3, int((kind >= 6).sum())))
     return base, np.zeros(n, np.int32), acts
 
 
@@ -239,7 +127,7 @@ def _events_ship(base, trace, n):
 def test_ship_dies_and_respawns_in_the_compared_tick(sfa, oracle_mod, gametype, n):
     """Feature 0 and the death timer of a ship killed by a shell, by each hexagon, and of one that respawns."""
     base, pv, acts = _setup_ship(oracle_mod, gametype, n)
-    trace = _oracle_trace(oracle_mod, gametype, base, pv, acts)
+    trace = oracle_trace(oracle_mod, gametype, base, pv, acts)
     _events_ship(base, trace, n)
     _lockstep(sfa, gametype, base, pv, acts, trace)
 
@@ -250,8 +138,8 @@ def _setup_missiles(O, gametype, n):
     """Lane i % 8: 0 a vlner increment, 1 a vlner reset, 2 a fortress destruction, 3 a miss, 4 increment then reset (two hits
     in one tick), 5 a hit and a miss in one tick, 6 a hit on a dead fortress, 7 nothing."""
     rng = np.random.default_rng(300 + n)
-    base = _fresh(O, gametype, n)
-    tab = _missile_table()
+    base = fresh(O, gametype, n)
+    tab = missile_table()
     kind = np.arange(n) % 8
 
     def put(i, s, hit):
@@ -279,7 +167,7 @@ def _setup_missiles(O, gametype, n):
             base["fort_alive"][i] = 0
             base["fort_death_timer"][i] = 34
     acts = np.zeros((2, n), np.uint8)
-    acts[1] = rng.integers(0, _n_actions(gametype), n)
+    acts[1] = rng.integers(0, n_actions(gametype), n)
     return base, base["vlner"].astype(np.int32), acts
 
 
@@ -304,7 +192,7 @@ def test_missile_outcomes_reach_the_late_features(sfa, oracle_mod, gametype, n):
     """Fortress alive, vlner, kill_ready and the missile count depend on what the missile wave hands over: every outcome of a
     missile, and two of them in one lane and tick."""
     base, pv, acts = _setup_missiles(oracle_mod, gametype, n)
-    trace = _oracle_trace(oracle_mod, gametype, base, pv, acts)
+    trace = oracle_trace(oracle_mod, gametype, base, pv, acts)
     _events_missiles(base, trace, n)
     _lockstep(sfa, gametype, base, pv, acts, trace)
 
@@ -314,7 +202,7 @@ def test_missile_outcomes_reach_the_late_features(sfa, oracle_mod, gametype, n):
 def _setup_keys(O, gametype, n):
     """Every key pressed in one tick and released in the next, lane i starting i % 8 ticks into the sequence; the timers start
     at values of their own, so that a missed zeroing shows."""
-    base = _fresh(O, gametype, n)
+    base = fresh(O, gametype, n)
     rng = np.random.default_rng(400 + n)
     for k in ("fire_timer", "thrust_timer", "left_timer", "right_timer"):
         base[k] = -rng.integers(3, 40, n)  # released for a while
@@ -340,7 +228,7 @@ def _events_keys(base, trace, gametype):
 def test_key_timers_on_press_and_release_edges(sfa, oracle_mod, gametype, n):
     """Features 15-18 (15-16) on a press and a release edge of every key in consecutive ticks."""
     base, pv, acts = _setup_keys(oracle_mod, gametype, n)
-    trace = _oracle_trace(oracle_mod, gametype, base, pv, acts)
+    trace = oracle_trace(oracle_mod, gametype, base, pv, acts)
     _events_keys(base, trace, gametype)
     _lockstep(sfa, gametype, base, pv, acts, trace)
 
@@ -354,9 +242,9 @@ def test_feature_14_real_and_mirrored(sfa, oracle_mod, gametype, real_shell_coun
     count, which the missile wave's events still change."""
     n = 256
     rng = np.random.default_rng(500 + len(gametype))
-    base, pv = _fuzz(oracle_mod, gametype, n, rng)
-    acts = rng.integers(0, _n_actions(gametype), (6, n)).astype(np.uint8)
-    trace = _oracle_trace(oracle_mod, gametype, base, pv, acts, real_shell_count)
+    base, pv = fuzz_sparse(oracle_mod, gametype, n, rng)
+    acts = rng.integers(0, n_actions(gametype), (6, n)).astype(np.uint8)
+    trace = oracle_trace(oracle_mod, gametype, base, pv, acts, real_shell_count=real_shell_count)
     f13 = np.array([tr[0][:, 13] for tr in trace])
     f14 = np.array([tr[0][:, 14] for tr in trace])
     assert (np.diff(f13, axis=0) < 0).any()  # missiles left in compared ticks
@@ -377,12 +265,12 @@ def test_forty_ticks_at_128_and_256_envs_per_workgroup(sfa, oracle_mod, gametype
     seeded sample of 256 lanes against the oracle, the last tile's lanes among them."""
     rng = np.random.default_rng(600 + n + len(gametype))
     T = 40
-    base, pv = _fuzz(oracle_mod, gametype, n, rng)
+    base, pv = fuzz_sparse(oracle_mod, gametype, n, rng)
     base["time"][rng.random(n) < 0.02] = 180000 - 34 * 20  # a few lanes start a new game on the way
     base["tick"] = base["time"] // 34
-    acts = rng.integers(0, _n_actions(gametype), (T, n)).astype(np.uint8)
+    acts = rng.integers(0, n_actions(gametype), (T, n)).astype(np.uint8)
     lanes = np.sort(np.concatenate([rng.choice(n - 64, 224, replace=False), n - 64 + rng.choice(64, 32, replace=False)]))
-    trace = _oracle_trace(oracle_mod, gametype, base[lanes], pv[lanes], acts[:, lanes])
+    trace = oracle_trace(oracle_mod, gametype, base, pv, acts, lanes)
     d = trace[-1][4]["stats"] - base["stats"][lanes]
     assert np.array([tr[2] for tr in trace]).any()  # new games among the sampled lanes (their statistics start over)
     assert (d[:, [ST_SHELL, ST_RESETS, ST_MISSED, ST_SHOTS]] > 0).any(0).all()

@@ -16,13 +16,10 @@ all of it) -- and holds them
 Shapes: 64 envs (one tile, 64 envs per workgroup), 16 448 (the first multiple of 64 above 16 384: 128 per workgroup) and
 32 832 (the first above 32 768: 256 per workgroup).  A tile is one of four blocks: `mixed` (lane % 16 = the scenarios of
 _block), `all` (every lane fires a missile AND a shell on the first tick), `one` (lane 37 alone fires a shell), `none`."""
-import os
-
 import numpy as np
 import pytest
 
-from sfcompare import compare_state, snapshots_to_fields
-from test_gpu_step_reorder import ST_SHELL, ST_SMALL, _fresh, _n_actions
+from lockstep import ST_SHELL, ST_SMALL, check_ticks, fresh, make_env, n_actions, oracle_trace, play, same_bytes, sfa
 
 pytestmark = pytest.mark.gpu
 
@@ -33,16 +30,6 @@ BLOCKS = ["mixed", "all", "one", "none"]
 SPF = 6       # sf_kernels.hip: SF_SPF, the shell slots the games' wave prefetches; slots beyond take its dependent-load loop
 LOCK = 1000   # sf_layout.h: lock_time
 MANY = (0, 2, 5, 9, 10, 14, 17, 19)
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def _block(O, gametype, who, seed):
@@ -58,7 +45,7 @@ def _block(O, gametype, who, seed):
       slot 1.
     Lanes 5, 7 and 15 play NOOP throughout."""
     rng = np.random.default_rng(seed)
-    base = _fresh(O, gametype, 64)
+    base = fresh(O, gametype, 64)
     base["ship_y"] = 315.0 + 9.0
     base["fort_angle"] = base["fort_last_angle"] = 10
     base["fort_timer"] = LOCK if who in ("mixed", "all") else 300
@@ -140,57 +127,29 @@ def _batch(O, gametype, n, blocks, T):
     small = np.concatenate([p[0] for p in parts])
     idx = np.arange(n) % len(small)
     base = small[idx].copy()
-    acts = rng.integers(0, _n_actions(gametype), (T, n)).astype(np.uint8)
+    acts = rng.integers(0, n_actions(gametype), (T, n)).astype(np.uint8)
     acts[0] = np.concatenate([p[1] for p in parts])[idx]
     acts[:, np.concatenate([p[2] for p in parts])[idx]] = 0
     who = np.array([blocks[(i // 64) % len(blocks)] for i in range(n)])
     return base, acts, who
 
 
-def _load(sfa, gametype, base, twin):
-    env = sfa.SFVecEnv(len(base), gametype=gametype)
-    for k, v in snapshots_to_fields(base).items():
-        env.set_field(k, v)
-    env.set_field("prev_vlner", np.zeros(len(base), np.int32))
-    if twin:
-        env.enable_final_obs()  # (the step leaves the split launch: the XTRA / FOBS instantiation, the same outputs)
-    return env
-
-
 def _play(sfa, O, gametype, base, acts, lanes=None):
-    """Both batches and the oracle (of `lanes` or of all lanes) in lock-step; returns the oracle's trace."""
+    """Both batches play `acts`; they are held to each other byte for byte and the first to the oracle (of `lanes` or of all
+    lanes): the state after every tick of a batch of up to 256 envs, else after the first and the last.  Returns the oracle's
+    trace."""
     n, T = len(base), len(acts)
-    sel = slice(None) if lanes is None else lanes
-    e1, e2 = _load(sfa, gametype, base, False), _load(sfa, gametype, base, True)
-    orc = O.OracleVecEnv(gametype, len(base[sel]))
-    orc.load_snapshots(base[sel], np.zeros(len(base[sel]), np.int32))
-    a = torch.from_numpy(np.ascontiguousarray(acts)).to(e1.device)
-    trace = []
-    for t in range(T):
-        o1 = [x.cpu().numpy() for x in e1.step_tensors(a[t])]
-        o2 = [x.cpu().numpy() for x in e2.step_tensors(a[t])]
-        for name, x, y in zip(("obs", "reward", "done", "info"), o1, o2):
-            assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), (t, name, np.argwhere(x != y)[:5].tolist())
-        obs, rew, done, info = o1
-        oo, orw, od, oi = orc.step(acts[t][sel].astype(np.int32))
-        snaps = orc.snapshots()
-        trace.append((oo, orw, od, oi, snaps))
-        want = oo.astype(np.float32)
-        bad = np.argwhere(obs[sel].view(np.uint32) != want.view(np.uint32))
-        assert bad.size == 0, (t, bad[:5].tolist(), obs[sel][bad[0][0]].tolist(), want[bad[0][0]].tolist())
-        assert np.array_equal(rew[sel], orw), (t, np.flatnonzero(rew[sel] != orw)[:5])
-        assert np.array_equal(done[sel].astype(bool), od) and np.array_equal(info[sel].astype(bool), oi), t
-        if n <= 256 or t == 0 or t == T - 1:
-            sd1, sd2 = e1.state_dict(), e2.state_dict()
-            for k in sd1:
-                x, y = np.ascontiguousarray(sd1[k]), np.ascontiguousarray(sd2[k])
-                assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), (t, k, np.argwhere(x != y)[:5].tolist())
-            bad = compare_state(sd1, snaps, lanes=lanes)
-            assert not bad, (t, bad)
-    for e in (e1, e2):
-        e.check_actions()
-        e.check_state()  # no hand-over poll gave up
-        e.close()
+    pv = np.zeros(n, np.int32)
+    e1, e2 = make_env(sfa, gametype, base, pv), make_env(sfa, gametype, base, pv)
+    e2.enable_final_obs()  # (the step leaves the split launch: the XTRA / FOBS instantiation, the same outputs)
+    state_at = lambda t: n <= 256 or t in (0, T - 1)
+    k1 = play(e1, acts, "step", state_at, check_state=True)  # (check_state: no hand-over poll gave up)
+    k2 = play(e2, acts, "step", state_at, check_state=True)
+    e1.close()
+    e2.close()
+    same_bytes(k1, k2)
+    trace = oracle_trace(O, gametype, base, pv, acts, lanes)
+    check_ticks(k1, trace, "f32_bits", lanes)
     return trace
 
 

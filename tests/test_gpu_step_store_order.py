@@ -11,8 +11,9 @@ lock-step with the CPU oracle and compares, after EVERY tick,
   * reward / done / info exactly,
   * every state field get_field reads back (sfcompare.compare_state: bit for bit; the shells' positions to 1e-9, the oracle's
     libm against the device's direction arithmetic, as everywhere),
-  * the rows of the output arrays BEHIND n_envs, which no lane may write (the outputs live in arenas with a sentinel tail;
-    the state of the padding lanes themselves is not reachable through the API).
+  * the rows of the output arrays BEHIND n_envs, which no lane may write (the outputs live in arenas with a sentinel tail,
+    looked at behind the last tick: nothing puts a sentinel back; the state of the padding lanes themselves is not reachable
+    through the API).
 
 The same cases run a second time in ONE fresh child process with SFMI_FORCE_SPLIT=1; its per-tick SHA-256 over the raw bytes of
 every output and every state field must equal this process's: the two launches agree byte for byte, shells included.
@@ -44,26 +45,23 @@ import sys
 import numpy as np
 import pytest
 
+from lockstep import (ST_INCS, ST_MISSED, ST_SHELL, ST_SHOTS, ST_SMALL, check_ticks, every, make_env, missile_table, n_actions, oracle_trace,
+                      play, sfa)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-GOLDEN = os.path.join(HERE, "golden")
 
-ST_SMALL, ST_SHELL, ST_MISSED, ST_SHOTS, ST_INCS = 1, 2, 6, 7, 11
 GAMETYPES = ["youturn", "autoturn"]
 SHAPES = [64, 256, 320]
 T = 6
 SENTINEL = 0x5A
 
 
-def _n_actions(gametype):
-    return 5 if gametype == "youturn" else 3  # action set 1: NOOP, FIRE, THRUST (, LEFT, RIGHT)
-
-
 # ---------------------------------------------------------------- the cases
 
 def _setup(O, gametype, n):
     rng = np.random.default_rng(7000 + n + len(gametype))
-    tab = np.load(os.path.join(GOLDEN, "tables.npz"))["missile_vel_by_angle"]
+    tab = missile_table()
     base = O.OracleVecEnv(gametype, n).snapshots()
     base["ship_x"], base["ship_y"] = 455.0, 315.0  # inside the big hexagon, outside the small one: nothing happens by itself
     base["ship_vx"], base["ship_vy"] = 0.0, 0.0
@@ -105,7 +103,7 @@ def _setup(O, gametype, n):
     acts = np.zeros((T, n), np.uint8)
     acts[0, kind == 4] = 1
     acts[2, kind == 4] = 1
-    acts[:, kind == 7] = rng.integers(2, _n_actions(gametype), (T, int((kind == 7).sum())))  # any key but FIRE
+    acts[:, kind == 7] = rng.integers(2, n_actions(gametype), (T, int((kind == 7).sum())))  # any key but FIRE
     return base, base["vlner"].astype(np.int32), acts
 
 
@@ -139,9 +137,7 @@ def _case(O, gametype, n):
     key = (gametype, n)
     if key not in _CASES:
         base, pv, acts = _setup(O, gametype, n)
-        orc = O.OracleVecEnv(gametype, n)
-        orc.load_snapshots(base, pv)
-        trace = [orc.step(acts[t].astype(np.int32)) + (orc.snapshots(),) for t in range(T)]
+        trace = oracle_trace(O, gametype, base, pv, acts)
         _check_events(base, trace, n)
         for x in (base, pv, acts):
             x.setflags(write=False)
@@ -162,56 +158,41 @@ def _arena(torch, env, rows):
     return big, tuple(b[:n] for b in big)
 
 
-def _make_env(m, torch, gametype, base, pv, f64=False):
-    from sfcompare import snapshots_to_fields
+def _play(m, gametype, base, pv, acts, f64=False):
+    """Step the batch tick by tick, the outputs in arenas.  Returns (Ticks with the state after every tick, the sha256 per
+    tick of all the outputs' and the state's bytes); asserts that nothing behind n_envs was written."""
+    import torch
 
-    env = m.SFVecEnv(len(base), gametype=gametype, obs_dtype=torch.float64 if f64 else torch.float32)
-    for k, v in snapshots_to_fields(base).items():
-        env.set_field(k, v)
-    env.set_field("prev_vlner", np.asarray(pv, np.int32))
-    return env
-
-
-def _play(m, torch, gametype, base, pv, acts, f64=False):
-    """Step the batch tick by tick.  Returns per tick ((obs, reward, done, info) as numpy, state_dict, sha256 of all their bytes);
-    asserts that nothing behind n_envs was written."""
     n = len(base)
-    env = _make_env(m, torch, gametype, base, pv, f64)
+    env = make_env(m, gametype, base, pv, f64=f64)
     big, out = _arena(torch, env, (n + 255) // 256 * 256)
-    a = torch.from_numpy(np.array(acts)).to(env.device)
-    ticks = []
+    ticks = play(env, acts, "step", every(1), out=out, check_state=True)
+    for b in big:  # (nothing puts the sentinel back: a tail still whole after the last tick was whole after every tick)
+        tail = b[n:].contiguous().view(torch.uint8).cpu().numpy()
+        assert (tail == SENTINEL).all(), ("written behind n_envs", tuple(b.shape))
+    env.close()
+    digests = []
     for t in range(len(acts)):
-        env.step_tensors(a[t], out=out)
-        res = tuple(x.cpu().numpy().copy() for x in out)
-        for b in big:
-            tail = b[n:].contiguous().view(torch.uint8).cpu().numpy()
-            assert (tail == SENTINEL).all(), ("written behind n_envs", t, tuple(b.shape))
-        sd = env.state_dict()
         h = hashlib.sha256()
-        for x in res:
+        for x in (ticks.obs[t], ticks.reward[t], ticks.done[t], ticks.info[t]):
             h.update(x.tobytes())
+        sd = ticks.states[t]
         for k in sorted(sd):
             h.update(k.encode() + np.ascontiguousarray(sd[k]).tobytes())
-        ticks.append((res, sd, h.hexdigest()))
-    env.check_actions()
-    env.check_state()
-    env.close()
-    return ticks
+        digests.append(h.hexdigest())
+    return ticks, digests
 
 
 def _child_main(path):
     """The child process: every case of the file `path`, its digests as one JSON line."""
     sys.path.insert(0, ROOT)
-    sys.path.insert(0, HERE)
-    import torch
-
     import spacefortress_amd as m
 
     z = np.load(path, allow_pickle=False)
     out = {}
     for name in json.loads(str(z["names"])):
         gametype, n = name.split(":")
-        out[name] = [h for _, _, h in _play(m, torch, gametype, z[name + ":base"], z[name + ":pv"], z[name + ":acts"])]
+        out[name] = _play(m, gametype, z[name + ":base"], z[name + ":pv"], z[name + ":acts"])[1]
     print("DIGESTS " + json.dumps(out), flush=True)
 
 
@@ -224,23 +205,13 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
-
-
 _PLAYED = {}
 
 
 def _played(sfa, O, gametype, n):
     if (gametype, n) not in _PLAYED:
         base, pv, acts, _ = _case(O, gametype, n)
-        _PLAYED[(gametype, n)] = _play(sfa, torch, gametype, base, pv, acts)
+        _PLAYED[(gametype, n)] = _play(sfa, gametype, base, pv, acts)
     return _PLAYED[(gametype, n)]
 
 
@@ -265,39 +236,23 @@ def forced_split_digests(oracle_mod, tmp_path_factory):
 
 
 def _against_oracle(ticks, trace, f64=False, lanes=None):
-    """Every tick's outputs and state against the oracle's (of `lanes` of the batch, or of all of it)."""
-    from sfcompare import compare_state
-
-    sel = slice(None) if lanes is None else lanes
-    for t, ((obs, rew, done, info), sd, _) in enumerate(ticks):
-        oo, orw, od, oi, snaps = trace[t]
-        obs, rew, done, info = obs[sel], rew[sel], done[sel], info[sel]
-        if f64:
-            want = oo
-            ok = np.abs(obs - want) <= 1e-9 * np.maximum(1.0, np.abs(want))  # (sfcompare.obs_close's bound for float64 rows)
-            assert ok.all(), (t, np.argwhere(~ok)[:5].tolist())
-        else:
-            want = oo.astype(np.float32)
-            bad = np.argwhere(obs.view(np.uint32) != want.view(np.uint32))
-            assert bad.size == 0, (t, bad[:5].tolist(), obs[bad[0][0]].tolist(), want[bad[0][0]].tolist())
-        assert rew.tobytes() == orw.astype(np.int32).tobytes(), (t, np.flatnonzero(rew != orw)[:5])
-        assert np.array_equal(done.astype(bool), od) and np.array_equal(info.astype(bool), oi), t
-        bad = compare_state(sd, snaps, lanes=lanes)
-        assert not bad, (t, bad)
+    """Every tick's outputs and state against the oracle's (of `lanes` of the batch, or of all of it): float32 rows as bit
+    patterns, float64 rows to sfcompare.obs_close's 1e-9."""
+    check_ticks(ticks, trace, "close_f64" if f64 else "f32_bits", lanes)
 
 
 @pytest.mark.parametrize("n", SHAPES)
 @pytest.mark.parametrize("gametype", GAMETYPES)
 def test_every_tick_against_the_oracle(sfa, oracle_mod, gametype, n):
     """The batch as launched by default: outputs and every state field after every tick."""
-    _against_oracle(_played(sfa, oracle_mod, gametype, n), _case(oracle_mod, gametype, n)[3])
+    _against_oracle(_played(sfa, oracle_mod, gametype, n)[0], _case(oracle_mod, gametype, n)[3])
 
 
 @pytest.mark.parametrize("n", SHAPES)
 @pytest.mark.parametrize("gametype", GAMETYPES)
 def test_forced_split_child_agrees_byte_for_byte(sfa, oracle_mod, forced_split_digests, gametype, n):
     """The same ticks in a fresh process with SFMI_FORCE_SPLIT=1: the digest of every output and state byte, tick by tick."""
-    mine = [h for _, _, h in _played(sfa, oracle_mod, gametype, n)]
+    mine = _played(sfa, oracle_mod, gametype, n)[1]
     theirs = forced_split_digests["%s:%d" % (gametype, n)]
     assert mine == theirs, [t for t in range(T) if mine[t] != theirs[t]]
 
@@ -306,7 +261,7 @@ def test_forced_split_child_agrees_byte_for_byte(sfa, oracle_mod, forced_split_d
 def test_float64_observations_one_tick_not_split(sfa, oracle_mod, gametype):
     """A float64-observation batch is stepped by the one-tick instantiations without a missile wave."""
     base, pv, acts, trace = _case(oracle_mod, gametype, 256)
-    _against_oracle(_play(sfa, torch, gametype, base, pv, acts, f64=True), trace, f64=True)
+    _against_oracle(_play(sfa, gametype, base, pv, acts, f64=True)[0], trace, f64=True)
 
 
 BIG = 32832                   # one tile past 32 768 envs: workgroups of 256 envs, the launches that store chunks early
@@ -322,11 +277,9 @@ def test_workgroups_of_256_envs(sfa, oracle_mod, gametype, f64):
     base, pv, acts, _ = _case(oracle_mod, gametype, 256)
     base, pv, acts = np.resize(base, BIG), np.resize(pv, BIG), np.stack([np.resize(a, BIG) for a in acts])
     lanes = np.concatenate([np.arange(64 * k, 64 * k + 64) for k in BIG_TILES])
-    orc = oracle_mod.OracleVecEnv(gametype, len(lanes))
-    orc.load_snapshots(base[lanes], pv[lanes])
-    trace = [orc.step(acts[t, lanes].astype(np.int32)) + (orc.snapshots(),) for t in range(T)]
+    trace = oracle_trace(oracle_mod, gametype, base, pv, acts, lanes)
     _check_events(base[lanes], trace, len(lanes))
-    _against_oracle(_play(sfa, torch, gametype, base, pv, acts, f64=f64), trace, f64=f64, lanes=lanes)
+    _against_oracle(_play(sfa, gametype, base, pv, acts, f64=f64)[0], trace, f64=f64, lanes=lanes)
 
 
 def _state_bytes(sd):
@@ -338,15 +291,14 @@ def test_rollout_of_four_ticks(sfa, oracle_mod, gametype):
     """The FUSED instantiation keeps its single store behind the tick loop: K = 4 ticks in one launch give the rows and leave
     the state of four single steps (which the tests above hold to the oracle), byte for byte."""
     base, pv, acts, trace = _case(oracle_mod, gametype, 256)
-    single = _played(sfa, oracle_mod, gametype, 256)
-    env = _make_env(sfa, torch, gametype, base, pv)
+    single = _played(sfa, oracle_mod, gametype, 256)[0]
+    env = make_env(sfa, gametype, base, pv)
     obs, rew, done, info = (x.cpu().numpy() for x in env.rollout(torch.from_numpy(np.array(acts[:4])).to(env.device)))
     assert np.array([tr[2] for tr in trace[:4]]).any()  # a new game inside the launch
     for t in range(4):
-        want = single[t][0]
-        assert obs[t].tobytes() == want[0].tobytes() and rew[t].tobytes() == want[1].tobytes(), t
-        assert done[t].tobytes() == want[2].tobytes() and info[t].tobytes() == want[3].tobytes(), t
-    assert _state_bytes(env.state_dict()) == _state_bytes(single[3][1])
+        assert obs[t].tobytes() == single.obs[t].tobytes() and rew[t].tobytes() == single.reward[t].tobytes(), t
+        assert done[t].tobytes() == single.done[t].tobytes() and info[t].tobytes() == single.info[t].tobytes(), t
+    assert _state_bytes(env.state_dict()) == _state_bytes(single.states[3])
     env.close()
 
 
@@ -366,7 +318,7 @@ def test_step_repeat_of_three_ticks(sfa, oracle_mod, gametype):
     ended = np.array([s[2] for s in steps]).any(0)
     assert ended.any() and not ended.all()
     keep = np.flatnonzero(~ended)
-    env = _make_env(sfa, torch, gametype, base, pv)
+    env = make_env(sfa, gametype, base, pv)
     obs, rew, done, info = (x.cpu().numpy() for x in env.step_repeat(torch.from_numpy(acts[0].copy()).to(env.device), 3))
     assert np.array_equal(done.astype(bool), ended)
     assert (env.last_ticks.cpu().numpy()[keep] == 3).all()

@@ -7,16 +7,11 @@ import os
 import numpy as np
 import pytest
 
+from lockstep import sfa
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 @pytest.mark.parametrize("gametype,obs_type,f64,n", [("youturn", "features", False, 4096), ("autoturn", "features", True, 1000),

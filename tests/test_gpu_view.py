@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from lockstep import load_state as _load, sfa
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -17,22 +18,6 @@ torch = pytest.importorskip("torch")
 VIEWS = os.path.join(GOLDEN, "views")
 GUI = (130, 80, 450, 460)
 FRAME_VIEWS = ["gui", "game", "gui_grey", "s077", "s078", "aniso"]
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
-
-
-def _load(env, snaps):
-    from sfcompare import snapshots_to_fields
-    for k, v in snapshots_to_fields(snaps).items():
-        env.set_field(k, v)
 
 
 def _same(got, want, what):

@@ -21,20 +21,11 @@ import pytest
 import bearingref as br
 from conftest import GOLDEN
 from test_wrapper_golden import EXTRAS, KILL_READY, OBS_TYPES, RUNS, WRAPPER, unmasked
+from lockstep import sfa
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def sfa():
-    import spacefortress_amd as m
-    from spacefortress_amd import _lib
-
-    assert os.path.exists(_lib.LIB_PATH), "libsfmi.so not built: the GPU tests never fall back"
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return m
 
 
 def _check(got, want, ot, what, stats):

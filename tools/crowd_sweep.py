@@ -6,7 +6,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import spacefortress_amd as sfa
 from oracle import oracle as O
 from oracle import render_np as R
-from test_gpu_parity import _fuzz_base, _load_both
+from lockstep import fuzz_crowded, load_both
 z = np.load(os.path.join(ROOT, "tests", "golden", "tables.npz"))
 hb, hs = z["hex_points"][:12], z["hex_points"][12:]
 bg = R.background(hb, hs)
@@ -14,10 +14,10 @@ tot = bad = 0
 for gt in ("youturn", "autoturn"):
     for seed in range(100, 106):
         n = 96
-        base, pv = _fuzz_base(O, gt, n, np.random.default_rng(seed))
+        base, pv = fuzz_crowded(O, gt, n, np.random.default_rng(seed))
         ang = np.degrees(np.arctan2(base["shell_vy"], base["shell_vx"]))
         base["shell_angle"] = np.where(ang < 0, ang + 360.0, ang)
-        env, orc = _load_both(sfa, O, gt, base, prev_vlner=pv)
+        env, orc = load_both(sfa, O, gt, base, prev_vlner=pv)
         raw = env.render("image-raw").cpu().numpy(); small = env.render("image").cpu().numpy()
         snaps = orc.snapshots()
         for i in range(n):
