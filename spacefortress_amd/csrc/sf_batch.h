@@ -93,7 +93,7 @@ struct sf_batch {
   DevBuf<uint32_t> d_bg;            // image observation: static background, 92*90 bytes
   DevBuf<uint32_t> d_bg84;          // ... resampled to 84x84
   DevBuf<double> d_arcs;            // the explosion's arc constants (sf_arc_table), then nothing
-  DevBuf<unsigned char> d_falpha;   // the live fortress's coverage at its 36 headings (sf_image_fort_alpha)
+  DevBuf<unsigned char> d_falpha;   // the live fortress's coverage at every whole-degree heading, 360 x 256 (sf_fort_alpha_table)
   DevBuf<uint32_t> d_tabs;          // INTER_AREA taps (sf_raster.h)
   DevBuf<unsigned char> d_xcache;   // explosion cache, SF_XC_BYTES per env; allocated by the first render
   // The missile fields as the reference has them (per env and slot), kept only while a caller looks at or edits them

@@ -38,17 +38,17 @@ extern "C" int sf_image_background_geom(int w, int h, double vx, double vy, doub
 }
 
 // the live fortress (SRC/draw.cpp:238-242: translate(355, 315) rotate(heading), four lines, ONE stroke) over the 16 x 16 box
-// the frame kernel keeps for it (sf_drawrec.h: kFpX0 ..), as 8-bit coverage, sector = heading / 10.  Heading 0 is the one
-// pose whose path is rectilinear under a matrix without rotation: cairo strokes that as boxes
+// the frame kernel keeps for it (sf_drawrec.h: kFpX0 ..), as 8-bit coverage, at a whole-degree heading 0..359.  Heading 0 is
+// the one pose whose path is rectilinear under a matrix without rotation: cairo strokes that as boxes
 // (cairo-path-stroke-boxes.c: _cairo_rectilinear_stroker) through the box converter, exact area instead of sub-rows.
-extern "C" int sf_image_fort_alpha(int sector, uint8_t* out256) {
-  if (sector < 0 || sector > 35 || !out256) {
-    sf_set_error("sf_image_fort_alpha: sector 0..35, out non-null");
+int sf_fort_alpha_heading(int heading, uint8_t* out256) {
+  if (heading < 0 || heading > 359 || !out256) {
+    sf_set_error("sf_fort_alpha_heading: heading 0..359, out non-null");
     return SF_ERR_ARG;
   }
   const sfh::Geometry g{SF_IMG_W, SF_IMG_H, (double)SF_IMG_W / 450.0, (double)SF_IMG_H / 460.0, SF_VP_X, SF_VP_Y, SF_LINE_W};
   std::vector<uint8_t> a((size_t)SF_IMG_W * SF_IMG_H, 0);
-  if (sector == 0) {
+  if (heading == 0) {
     static const double L[4][4] = {{0, 0, 36, 0}, {0, -18, 18, -18}, {18, -18, 18, 18}, {18, 18, 0, 18}};
     const sft::Affine v = sft::view_matrix(g.sx, g.sy, g.vp_x, g.vp_y);
     const sft::Affine m = sft::object_matrix(v, 355.0, 315.0, 1.0, 0.0);
@@ -64,8 +64,8 @@ extern "C" int sf_image_fort_alpha(int sector, uint8_t* out256) {
     sfh::boxes_cover(bx, 4, g.w, g.h, 255, a.data());  // white on black: the pixel IS the alpha
   } else {
     double cs[2];
-    sf_trig_deg(10 * sector, cs);
-    const sfh::Object ob = sfh::wireframe_object(1, 355.0, 315.0, 10 * sector, g, cs);
+    sf_trig_deg(heading, cs);
+    const sfh::Object ob = sfh::wireframe_object(1, 355.0, 315.0, heading, g, cs);
     std::vector<int> acc((size_t)g.w * g.h, 0);
     sfh::object_coverage(ob, g.w, g.h, acc.data());
     for (int i = 0; i < g.w * g.h; i++) a[i] = (uint8_t)sft::area_to_alpha(acc[i]);
@@ -80,6 +80,25 @@ extern "C" int sf_image_fort_alpha(int sector, uint8_t* out256) {
         return SF_ERR_ARG;
       }
   return SF_OK;
+}
+// ... of sector = heading / 10, the headings the game makes (SRC/game.cpp:206)
+extern "C" int sf_image_fort_alpha(int sector, uint8_t* out256) {
+  if (sector < 0 || sector > 35 || !out256) {
+    sf_set_error("sf_image_fort_alpha: sector 0..35, out non-null");
+    return SF_ERR_ARG;
+  }
+  return sf_fort_alpha_heading(10 * sector, out256);
+}
+// ... and of all 360 headings, 360 x 256 bytes, made once per process: a state may hold any of them (sf_set_field), and then the
+// frame kernel draws the fortress in place from this table (sf_drawrec.h: such a heading has no background)
+const uint8_t* sf_fort_alpha_table() {
+  static const std::vector<uint8_t> table = [] {
+    std::vector<uint8_t> t(360 * 256);
+    for (int h = 0; h < 360; h++)
+      if (sf_fort_alpha_heading(h, t.data() + 256 * h) != SF_OK) return std::vector<uint8_t>();
+    return t;
+  }();
+  return table.empty() ? nullptr : table.data();
 }
 
 // drawExplosion's arcs (SRC/draw.cpp:116-145) as sft::ArcK, 8 doubles each: [12 ring + k] for ring 0..6, then the circle's two

@@ -98,7 +98,7 @@ int sfb_ensure_render_resources(sf_batch* b, hipStream_t stream) {
   return SF_OK;
 }
 
-// The image observation tables of a new batch (sf_image.cpp): 11 KB, built for every batch so that sf_render works whatever
+// The image observation tables of a new batch (sf_image.cpp): 101 KB, built for every batch so that sf_render works whatever
 // obs_type the batch steps with (the reference's render(), ENV:190-193)
 int sfb_create_image_tables(sf_batch* b) {
   static_assert(SF_IMG_W == SF_IMAGE_W && SF_IMG_H == SF_IMAGE_H && SF_OUT == SF_IMAGE_OUT, "sfmi.h vs sf_raster.h");
@@ -112,11 +112,11 @@ int sfb_create_image_tables(sf_batch* b) {
   HIP_TRY(hipMemset(b->d_bg.get(), 0, (size_t)SF_BG_COUNT * SF_BG_STRIDE));
   static_assert(SF_OUT * SF_OUT % sizeof(uint32_t) == 0 && SF_BG_STRIDE % sizeof(uint32_t) == 0, "backgrounds in whole words");
   std::vector<double> arcs(86 * 8);
-  std::vector<uint8_t> fa(36 * 256);
   SF_TRY(sf_arc_table(arcs.data()));
-  for (int k = 0; k < 36; k++) SF_TRY(sf_image_fort_alpha(k, fa.data() + 256 * k));
+  const uint8_t* fa = sf_fort_alpha_table();
+  if (!fa) return SF_ERR_ARG;
   SF_TRY(upload(b->d_arcs, arcs.data(), arcs.size()));
-  SF_TRY(upload(b->d_falpha, fa.data(), fa.size()));
+  SF_TRY(upload(b->d_falpha, fa, (size_t)360 * 256));
   SF_TRY(upload(b->d_tabs, tabs, (size_t)SF_TAB_WORDS));
   // the score text: the built-in glyph atlas (sf_glyphs.h) and the four static backgrounds made with it
   HIP_TRY(b->d_glyphs.alloc(1));

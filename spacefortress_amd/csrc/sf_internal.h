@@ -58,6 +58,9 @@ hipError_t sf_launch_render(const unsigned char* state, const unsigned char* dra
 // the score / bar pictures (SF_HUD_BYTES, sf_raster.h)
 hipError_t sf_launch_hud_pictures(const uint32_t* bg, const uint32_t* bg84, const uint32_t* tabs, unsigned char* hud,
                                   const SfGlyphAtlas* glyphs, hipStream_t stream);
+// sf_image.cpp: the live fortress's coverage over its 16 x 16 box at heading 0..359; all 360 of them (nullptr: see sf_last_error)
+int sf_fort_alpha_heading(int heading, uint8_t* out256);
+const uint8_t* sf_fort_alpha_table();
 // ... and the 36 x 4 backgrounds with the fortress in them, behind the four plain ones (SF_BG_COUNT, sf_raster.h)
 hipError_t sf_launch_fort_patches(uint32_t* bg, uint32_t* bg84, const uint32_t* tabs, unsigned char* fpatch, const double* arcs,
                                   const unsigned char* falpha, hipStream_t stream);

@@ -752,7 +752,7 @@ struct SfRenderArgs {
   const unsigned char* hud;  // SF_HUD_BYTES: the score / bar pictures (sf_hud_kernel), or null
   const double* trig;        // cos, sin of deg2rad(k), k = 0 .. 359, as the reference's libm gives them (sf_trig_table)
   const double* arcs;        // 86 x 8: the explosion's arcs (sft::ArcK; sf_arc_table)
-  const unsigned char* falpha;  // 36 x 256: the live fortress's coverage over its 16 x 16 box, heading 10 k (sf_image_fort_alpha)
+  const unsigned char* falpha;  // 360 x 256: the live fortress's coverage over its 16 x 16 box, by heading (sf_fort_alpha_table)
   const SfGlyphAtlas* glyphs;   // the score text's glyph atlas (sf_glyphs.h); null or gw == 0: the seven-segment fallback
 };
 
@@ -864,10 +864,10 @@ __device__ __forceinline__ void fort_patch_copy(const Frame<RESIZE>& F, unsigned
 
 
 // the live fortress drawn IN PLACE (something the ship drew lies under it): its four lines are one cairo_stroke whose coverage
-// depends on the heading alone -- an alpha map per sector, made by the host (sf_image_fort_alpha) --, white, lerped in
+// depends on the heading alone -- an alpha map per whole degree, made by the host (sf_fort_alpha_table) --, white, lerped in
 template <bool RESIZE>
-__device__ __forceinline__ void fort_in_place(const Frame<RESIZE>& F, const unsigned char* falpha, int sector) {
-  const uint32_t aw = reinterpret_cast<const uint32_t*>(falpha + 256 * sector)[F.lane];  // four pixels of a row of sixteen
+__device__ __forceinline__ void fort_in_place(const Frame<RESIZE>& F, const unsigned char* falpha, int heading) {
+  const uint32_t aw = reinterpret_cast<const uint32_t*>(falpha + 256 * heading)[F.lane];  // four pixels of a row of sixteen
   uint8_t* p = F.fb + (kFpY0 + (F.lane >> 2)) * SF_IMG_W + kFpX0 + (F.lane & 3) * 4;
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -1284,7 +1284,7 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   } else {  // (rare: the ship, or its explosion, next to the fortress or its explosion: the reference's order, one by one)
     F.draw_strokes(mq, dvalid && lane < 3, dobj, dkind);
     if (fort_explodes_in_place) draw_explosion(F, a.arcs, sfc::fort_x, sfc::fort_y);
-    else fort_in_place(F, a.falpha, min(max((int)(int16_t)(hd[SF_DRW_ANGLES] >> 16) / 10, 0), 35));
+    else fort_in_place(F, a.falpha, min(max((int)(int16_t)(hd[SF_DRW_ANGLES] >> 16), 0), 359));  // (clamped like line_quad's)
     F.draw_strokes(mq, dvalid && lane >= kFirstMissileLane, dobj, dkind);
   }
   if (fl & SF_DRF_MISSILE19) {  // (the twentieth missile: its strokes have no lanes of their own)
@@ -1377,7 +1377,7 @@ __global__ __launch_bounds__(64, SF_RENDER_WPE) void sf_render_kernel(SfRenderAr
   }
 }
 
-// one workgroup per sector: the live fortress on the bare background -- its alpha map (the host's: sf_image_fort_alpha)
+// one workgroup per sector: the live fortress on the bare background -- its alpha map (the host's: sf_fort_alpha_table)
 // lerped in like a frame does in place --, its box of the surface and of the 84x84 image saved for fort_patch_copy; workgroup 36:
 // the destroyed fortress's explosion, drawn by the frames' own code
 __global__ __launch_bounds__(64) void sf_fort_patch_kernel(const uint32_t* bg, const uint32_t* bg84, const uint32_t* tabs,
@@ -1397,7 +1397,7 @@ __global__ __launch_bounds__(64) void sf_fort_patch_kernel(const uint32_t* bg, c
     ship_explosion(F, arcs, fpatch + 36 * SF_FP_BYTES, sfc::fort_x, sfc::fort_y);  // (a zeroed entry: draws and fills it)
     return;
   }
-  fort_in_place(F, falpha, sector);
+  fort_in_place(F, falpha, 10 * sector);
   // (the rest of the patch keeps the background's values, exactly as when the fortress is drawn in place)
   __syncthreads();
   fort_patch_copy(F, fpatch + sector * SF_FP_BYTES, true);
