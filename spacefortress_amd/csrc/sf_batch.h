@@ -136,6 +136,9 @@ struct sf_batch {
   unsigned long long* d_lrefused = nullptr;
   DevBuf<unsigned char> d_lrows;
   long lrows_cap = 0;
+  // sf_step_where (sfmi_hold.h): where the held envs wait while the others tick -- a buffer of the state's size, tile
+  // layout, made by the first masked step
+  DevBuf<unsigned char> d_hold;
 };
 
 inline bool sfb_is_image(const sf_batch* b) { return b->obs_mode == SF_OBS_IMAGE || b->obs_mode == SF_OBS_IMAGE_RAW; }

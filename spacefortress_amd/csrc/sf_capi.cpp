@@ -285,6 +285,7 @@ struct StepLaunch {
   uint8_t* act_out = nullptr;  // the sampled actions
   double *n_partials = nullptr, *n_ret = nullptr;  // the normaliser's partial sums and returns
   double n_gamma = 0.0;
+  const uint8_t* active = nullptr;  // sf_step_where: uint8 [n_envs], zero = the env is held around the launch (sfmi_hold.h)
 };
 
 static int check_act_type(const char* who, int act_type) {
@@ -294,6 +295,18 @@ static int check_act_type(const char* who, int act_type) {
   }
   return SF_OK;
 }
+
+// a step launch of launch_steps: if it fails behind a queued hold-begin, the held envs are still put back (their chunks and pool
+// entries live only in the stash, which the next masked step overwrites) before the error is returned
+#define STEP_TRY(expr)                                                                              \
+  do {                                                                                              \
+    const hipError_t e_ = (expr);                                                                   \
+    if (e_ != hipSuccess) {                                                                         \
+      (void)held_back();                                                                            \
+      sf_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);      \
+      return SF_ERR_HIP;                                                                            \
+    }                                                                                               \
+  } while (0)
 
 // guard -> flush -> launch -> draw_current -> frames: the one path from an entry point to sf_launch_step / sf_launch_step_repeat
 static int launch_steps(sf_batch* b, const StepLaunch& d, void* obs_dev, void* stream) {
@@ -315,16 +328,26 @@ static int launch_steps(sf_batch* b, const StepLaunch& d, void* obs_dev, void* s
   }
   const void* actions = sampled ? b->d_actrec.get() : d.actions;
   SF_FLUSH_VIEW(b, stream);
+  // a masked step: the held envs leave in front of the launch and come back behind it, with their output rows -- and, image
+  // batches, their draw records -- in front of the frames
+  if (d.active) HIP_TRY(sf_launch_hold_begin(args, d.active, b->d_hold.get(), (hipStream_t)stream));
+  const auto held_back = [&]() -> hipError_t {
+    if (!d.active) return hipSuccess;
+    return sf_launch_hold_end(args, d.active, b->d_hold.get(), image ? nullptr : obs_dev, d.reward, d.done, d.info, d.ticks,
+                              d.repeat == 1, (hipStream_t)stream);  // (sf_step says no ticks: every active env played its one)
+  };
   if (d.repeat > 1) {  // one REPEAT launch; an image batch's frame: one sfb_render from the draw records it left
-    HIP_TRY(sf_launch_step_repeat(args, b->autoturn, b->preset.shaped != 0, actions, d.act_type, image ? nullptr : obs_dev, d.reward,
+    STEP_TRY(sf_launch_step_repeat(args, b->autoturn, b->preset.shaped != 0, actions, d.act_type, image ? nullptr : obs_dev, d.reward,
                                   d.done, d.info, d.ticks, d.repeat, (hipStream_t)stream));
+    HIP_TRY(held_back());
     b->draw_current = b->args.draw != nullptr;  // (the draw records of the state the window ends in)
     if (image && obs_dev) return sfb_render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
     return SF_OK;
   }
   if (!(image && obs_dev)) {
-    HIP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, actions, d.act_type, image ? nullptr : obs_dev, d.reward,
+    STEP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, actions, d.act_type, image ? nullptr : obs_dev, d.reward,
                            d.done, d.info, d.n_steps, d.fused, (hipStream_t)stream));
+    HIP_TRY(held_back());
     b->draw_current = b->args.draw != nullptr;  // (an image batch's step launch leaves the draw records of the new state)
     return SF_OK;
   }
@@ -337,16 +360,18 @@ static int launch_steps(sf_batch* b, const StepLaunch& d, void* obs_dev, void* s
     SfKernelArgs at = args;
     if (at.act_out) at.act_out += row;
     if (at.events) at.events += row;
-    HIP_TRY(sf_launch_step(at, b->autoturn, b->preset.shaped != 0,
+    STEP_TRY(sf_launch_step(at, b->autoturn, b->preset.shaped != 0,
                            sampled ? actions : (const unsigned char*)actions + row * (size_t)d.act_type, d.act_type, nullptr,
                            d.reward ? d.reward + row : nullptr, d.done ? d.done + row : nullptr, d.info ? d.info + row : nullptr,
                            1, false, (hipStream_t)stream));
+    HIP_TRY(held_back());  // (a masked step is one tick: n_steps == 1)
     b->draw_current = b->args.draw != nullptr;
     const int rc = sfb_render(b, b->obs_mode, (uint8_t*)obs_dev + row * frame, 0, (hipStream_t)stream);
     if (rc != SF_OK) return rc;
   }
   return SF_OK;
 }
+#undef STEP_TRY
 
 extern "C" int sf_step(sf_batch* b, const void* actions_dev, int act_type, void* obs_dev, int32_t* reward_dev,
                        uint8_t* done_dev, uint8_t* info_dev, void* stream) {
@@ -383,6 +408,33 @@ extern "C" int sf_step_repeat(sf_batch* b, const void* actions_dev, int act_type
   DeviceGuard guard(b->device);
   if (ticks_dev) HIP_TRY(hipMemsetAsync(ticks_dev, 1, (size_t)b->n_envs, (hipStream_t)stream));
   return SF_OK;
+}
+
+// sfmi_hold.h.  launch_steps' path with the two hold launches around the step launch; the stash is the batch's, made here once.
+extern "C" int sf_step_where(sf_batch* b, const uint8_t* active_dev, const void* actions_dev, int act_type, int repeat, void* obs_dev,
+                             int32_t* reward_dev, uint8_t* done_dev, uint8_t* info_dev, uint8_t* ticks_dev, void* stream) {
+  if (!b || !active_dev || !actions_dev) {
+    sf_set_error("sf_step_where: null batch, mask or actions (the mask: uint8 [n_envs] on the device, non-zero = the env steps)");
+    return SF_ERR_ARG;
+  }
+  if (check_act_type("sf_step_where", act_type) != SF_OK) return SF_ERR_ARG;
+  if (repeat < 1 || repeat > 255) {
+    sf_set_error("sf_step_where: repeat must be in [1, 255] (got %d)", repeat);
+    return SF_ERR_ARG;
+  }
+  if (repeat > 1 && !b->args.auto_reset) {
+    sf_set_error("sf_step_where: a SF_FLAG_NO_AUTO_RESET batch has no action repeat (sf_step_repeat: an ACTIVE env that finishes "
+                 "inside the window would be given its new game); step such a batch with repeat 1");
+    return SF_ERR_ARG;
+  }
+  if (!b->d_hold) {  // the first masked step of this batch (not capturable: it allocates)
+    DeviceGuard guard(b->device);
+    HIP_TRY(b->d_hold.alloc(b->state_bytes));
+    HIP_TRY(hipMemsetAsync(b->d_hold.get(), 0, b->state_bytes, (hipStream_t)stream));
+  }
+  StepLaunch d{"sf_step_where", actions_dev, act_type, 1, false, reward_dev, done_dev, info_dev, repeat, ticks_dev};
+  d.active = active_dev;
+  return launch_steps(b, d, obs_dev, stream);
 }
 
 int sf_step_with_norm_partials(sf_batch* b, const void* actions_dev, int act_type, void* obs_dev, int32_t* reward_dev,

@@ -6,6 +6,7 @@
 #include "sf_glyphs.h"
 #include "sf_layout.h"
 #include "sfmi.h"
+#include "sfmi_hold.h"
 #include "sfmi_masked.h"
 #include "sfmi_repeat.h"
 
@@ -23,6 +24,13 @@ hipError_t sf_launch_step_repeat(const SfKernelArgs& a, bool autoturn, bool shap
 hipError_t sf_launch_reset_lanes(const SfKernelArgs& a, const uint8_t* mask, void* obs, hipStream_t stream);
 // the envs' draw records (sf_drawrec.h) from the state as it is: a.draw / a.draw_pics say where and for which pictures
 hipError_t sf_launch_drawrec(const SfKernelArgs& a, hipStream_t stream);
+// sf_step_where (sfmi_hold.h): around a step launch, the envs whose byte of active [n_envs] is zero are swapped for a game in
+// which nothing can happen and back.  stash: a buffer of the state's size.  End: the held envs' output rows (each may be
+// null; a.events and a.hint as the batch has them) and, where a.draw is set, their draw records from the restored state.
+// one_tick: the launch in between was a plain step, which writes no ticks: every active env's are 1
+hipError_t sf_launch_hold_begin(const SfKernelArgs& a, const uint8_t* active, unsigned char* stash, hipStream_t stream);
+hipError_t sf_launch_hold_end(const SfKernelArgs& a, const uint8_t* active, const unsigned char* stash, void* obs, int32_t* reward,
+                              uint8_t* done, uint8_t* info, uint8_t* ticks, int one_tick, hipStream_t stream);
 
 // gather (to_linear) / scatter one field between the tiled state and a linear [count][n_envs] buffer
 hipError_t sf_launch_field_copy(unsigned char* state, int n_envs, int field, unsigned char* linear, int to_linear,

@@ -1,5 +1,6 @@
 // sf_state_ops.hip -- the state tools: kernels that read or rewrite the tiled state off the hot path -- the masked reset, the
-// draw records from the state, sf_get_field / sf_set_field, the slot view of the missile pools, the lane states.  They share
+// draw records from the state, sf_get_field / sf_set_field, the slot view of the missile pools, the lane states, the two
+// launches around a masked step (sf_step_where).  They share
 // sf_lane_dev.h with sf_kernels.hip and nothing else: a change here leaves the step kernel's code object alone.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -107,9 +108,9 @@ hipError_t sf_launch_reset_lanes(const SfKernelArgs& a, const uint8_t* mask, voi
 // symbolic observation and renders now and then.  One wave per tile, a lane per env; the pool's entries file their
 // transforms at [owner][slot] and tell their owners through LDS where they come near the score / the bar, exactly like the
 // step kernel's m_row.  Same functions, same values: tests/test_gpu_image.py compares the two byte for byte.
-__global__ __launch_bounds__(64) void sf_drawrec_kernel(const unsigned char* state, int n_envs, unsigned char* draw, int pics) {
-  __shared__ unsigned near[64];
-  typedef float f4_t __attribute__((ext_vector_type(4)));
+// `take`: the lanes whose records are written (wave-uniform; all of them for sf_drawrec_kernel, the held ones behind a masked step).
+__device__ __forceinline__ void drawrec_tile(const unsigned char* state, int n_envs, unsigned char* draw, int pics, unsigned long long take,
+                                             unsigned* near) {
   const unsigned lane = threadIdx.x;
   const long tile_i = blockIdx.x;
   const unsigned char* tb = state + tile_i * sfl::kTileBytes;
@@ -123,6 +124,7 @@ __global__ __launch_bounds__(64) void sf_drawrec_kernel(const unsigned char* sta
   near[lane] = 0u;
   __syncthreads();
   pool_for_each(tb, (unsigned)__builtin_amdgcn_readfirstlane(mi.z), lane, [&](unsigned i, unsigned m) {  // (the same word's count in every lane)
+    if (!((take >> SF_MM_OWNER(m)) & 1ull)) return;
     const d2_t p = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), i * 16u);
     *reinterpret_cast<d2_t*>(dr + (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_MISSILE0 + SF_MM_SLOT(m)) * SF_DR_PIECE_STRIDE + SF_MM_OWNER(m) * SF_DR_LANE_STRIDE) = p;
     *reinterpret_cast<int16_t*>(dr + SF_DR_ANGLES_OFF + 2 * SF_MM_SLOT(m) + SF_MM_OWNER(m) * SF_DR_LANE_STRIDE) = (int16_t)SF_MM_ANGLE(m);
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(64) void sf_drawrec_kernel(const unsigned char* sta
   }
   __syncthreads();
   proj |= near[lane];
-  if (tile_i * 64 + lane >= n_envs) return;
+  if (tile_i * 64 + lane >= n_envs || !((take >> lane) & 1ull)) return;
   const int ship_angle = (int16_t)(sm.x & 0xFFFF), fort_angle = (int16_t)((unsigned)sm.x >> 16);
   const unsigned fl = ((unsigned)sm.y >> 16) & 0xFFu;
   const sfd::Header h = sfd::make_header(sp.x, sp.y, ship_angle, (fl & SF_FL_SHIP_ALIVE) != 0u, (fl & SF_FL_FORT_ALIVE) != 0u, fort_angle,
@@ -148,6 +150,11 @@ __global__ __launch_bounds__(64) void sf_drawrec_kernel(const unsigned char* sta
   *reinterpret_cast<u4_t*>(me) = u4_t{h.w[0], h.w[1], h.w[2], h.w[3]};
   *reinterpret_cast<u4_t*>(me + SF_DR_PIECE_STRIDE) = u4_t{h.w[4], h.w[5], h.w[6], h.w[7]};
   *reinterpret_cast<d2_t*>(me + (SF_DR_PIECE_OBJ0 + SF_DR_OBJ_SHIP) * SF_DR_PIECE_STRIDE) = sp;
+}
+
+__global__ __launch_bounds__(64) void sf_drawrec_kernel(const unsigned char* state, int n_envs, unsigned char* draw, int pics) {
+  __shared__ unsigned near[64];
+  drawrec_tile(state, n_envs, draw, pics, ~0ull, near);
 }
 
 hipError_t sf_launch_drawrec(const SfKernelArgs& a, hipStream_t stream) {
@@ -402,6 +409,24 @@ __device__ __forceinline__ unsigned sf_ls_chunk_off(int p, unsigned l) {
          16u * l;
 }
 
+// The observation rows of the lanes a state tool has just put into a tile (sf_lanes_load_kernel, sf_hold_end_kernel), by the
+// whole wave: `stage` = the tile's seven one-slot chunks in tile layout, in LDS (defined values in every lane), `write` = this
+// lane's row is wanted.  The step kernel's unpackers and write_obs; the bearings as the tick that made the state computed
+// them: a new game's (time 0: sf_reset, an auto-reset) with the reset's atan2 and its SF_FLAG_REF_RESET_OBS, any other with
+// the step's table form.
+__device__ __forceinline__ void obs_rows_from_stage(const SfKernelArgs& a, const unsigned char* stage, unsigned lane, bool write, void* obs,
+                                                    size_t e) {
+  Lane L;
+  const Off o = {lane * 16u, lane * 8u, lane * 4u, lane * 2u, lane};
+  load_lane_early(stage, o, L);
+  unpack_lane_late(load_lane_late(stage, o), L);
+  const bool fresh = L.time == 0;
+  const double* atab = a.consts + SF_CONST_ATAB;
+  const Extras x = fresh ? new_game_extras(a, L)
+                         : compute_extras(a, L, sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x, atab), sf_atan2_core(L.vy, L.vx, atab));
+  if (write) write_obs_row(a, obs, e, L, x);
+}
+
 __global__ __launch_bounds__(64) void sf_lanes_save_kernel(const unsigned char* state, int n_envs, const void* lanes, int idx64,
                                                           unsigned char* rows, u4_t header, unsigned long long* refused) {
   __shared__ d2_t mpos[SF_NSLOT];
@@ -546,19 +571,7 @@ __global__ __launch_bounds__(64) void sf_lanes_load_kernel(SfKernelArgs a, const
     }
     map[e] = -1;
     if (lane == 0) tflag[t] = 0u;
-    if (obs != nullptr && a.obs_type != 3 && rmask != 0ull) {  // (uniform)
-      Lane L;
-      const Off o = {lane * 16u, lane * 8u, lane * 4u, lane * 2u, lane};
-      load_lane_early(stage, o, L);
-      unpack_lane_late(load_lane_late(stage, o), L);
-      // the bearings as the tick that made this state computed them: a new game's (time 0: sf_reset, an auto-reset) with the
-      // reset's atan2 and its SF_FLAG_REF_RESET_OBS, any other with the step's table form
-      const bool fresh = L.time == 0;
-      const double* atab = a.consts + SF_CONST_ATAB;
-      const Extras x = fresh ? new_game_extras(a, L)
-                             : compute_extras(a, L, sf_atan2<true>(L.sy - sfc::fort_y, L.sx - sfc::fort_x, atab), sf_atan2_core(L.vy, L.vx, atab));
-      if (restored) write_obs_row(a, obs, (size_t)e, L, x);
-    }
+    if (obs != nullptr && a.obs_type != 3 && rmask != 0ull) obs_rows_from_stage(a, stage, lane, restored, obs, (size_t)e);  // (uniform)
     __syncthreads();  // (the LDS rows are the next tile's)
   }
 }
@@ -583,5 +596,183 @@ hipError_t sf_launch_lanes_load(const SfKernelArgs& a, const void* lanes, int id
   const long tiles = a.lanes / 64;
   const unsigned grid = (unsigned)(n < tiles ? n : tiles);
   hipLaunchKernelGGL(sf_lanes_load_kernel, dim3(grid), dim3(64), 0, stream, a, rows, row_idx, idx64, map, tflag, tlist, tcount, obs);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// sf_step_where (sfmi_hold.h): the envs whose byte of active [n_envs] is zero are HELD while the others tick.  The tick is
+// straight-line code with wave-wide ballots over a pool the tile shares, so a held lane cannot sit a launch out; instead
+// sf_hold_begin_kernel swaps it for a game in which nothing can happen -- the state a REPEAT launch parks a finished env in
+// (sf_kernels.hip, "PARKED") --, the unchanged step launch ticks that, and sf_hold_end_kernel swaps the lane back and rewrites
+// its outputs.  One wave per tile, a lane per env; both kernels return before they write anything in a tile without a held
+// env, and read no mask byte at or beyond n_envs: the lanes behind the batch in a partial last tile count as active.
+//
+// The stash is one more buffer in the tile layout.  A held lane's 47 chunks go to their own place in the stash's tile, its
+// missiles -- out of the pool by owner and slot -- to row `slot`, lane `owner` of the stash's missile_pos / missile_meta
+// rows (64 x SF_NSLOT entries: exactly the room), only the live ones.  Per held env and call 752 B read + 752 B written
+// twice, 20 B more per live missile, 112 B of inert chunks; every access is a 16-byte piece of a 1 KiB row the wave moves
+// whole.  Lane rows (sf_lanes_save_kernel's format) would move 1 136 B per copy, a third more, in 71-piece runs of one lane each.
+//
+// The inert game: ship dead with death_t = -(1 << 24) (no respawn: 255 ticks add 8 670), no missile, no shell (a dead ship
+// does not fire, the fortress fires at a live ship only), time 0 (no game over for 5 295 ticks), vlner = prev_vlner = 0 and every
+// per-episode counter and key timer zero (no reward, nothing that could leave its packed width: the overflow count of a
+// batch without auto-reset stays).  Position, velocity, headings, the fortress's timers, the score and the spawn cursor stay
+// the lane's own: nothing reads them to any effect.  tests/test_hold_model.py plays this recipe on the CPU oracle.
+namespace {
+constexpr int kInertDeath = -(1 << 24);
+
+__device__ __forceinline__ u4_t* hold_chunk(unsigned char* tile, int p, unsigned lane) {  // piece p (1 .. 47) as a row has it
+  return reinterpret_cast<u4_t*>(tile + sf_ls_chunk_off(p, lane));
+}
+}  // namespace
+
+__global__ __launch_bounds__(64) void sf_hold_begin_kernel(SfKernelArgs a, const uint8_t* active, unsigned char* stash) {
+  __shared__ d2_t spos[64][SF_NSLOT];
+  __shared__ unsigned short sang[64][SF_NSLOT];
+  const unsigned lane = threadIdx.x;
+  const long tile_i = blockIdx.x;
+  const long e = tile_i * 64 + lane;
+  const bool held = e < a.n_envs && active[e] == 0;
+  const unsigned long long hmask = __ballot(held);
+  if (hmask == 0ull) return;  // (uniform)
+  unsigned char* const tb = a.state + (size_t)tile_i * sfl::kTileBytes;
+  unsigned char* const sb = stash + (size_t)tile_i * sfl::kTileBytes;
+  // everything that is read from the tile's pool, first: the held lanes' entries into the stash, the others' through LDS
+  const unsigned mw = SF_LD(unsigned, SF_CHUNK(misc, 0), 16u * lane + 8u);
+  pool_for_each(tb, (unsigned)__builtin_amdgcn_readfirstlane(mw), lane, [&](unsigned i, unsigned m) {  // (the same word's count in every lane)
+    const unsigned ow = SF_MM_OWNER(m), s = SF_MM_SLOT(m);
+    const d2_t p = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), i * 16u);
+    if ((hmask >> ow) & 1ull) {
+      *reinterpret_cast<d2_t*>(sb + sfl::chunk_offset(SF_G_missile_pos, 0) + (size_t)(s * 64u + ow) * 16) = p;
+      *reinterpret_cast<unsigned*>(sb + sfl::chunk_offset(SF_G_missile_meta, 0) + (size_t)(s * 64u + ow) * 4) = SF_MM_ANGLE(m);
+    } else {
+      spos[ow][s] = p;
+      sang[ow][s] = (unsigned short)SF_MM_ANGLE(m);
+    }
+  });
+  const unsigned kept = held ? 0u : (mw & SF_MASK_LOW);
+  __syncthreads();
+  const unsigned wp = pool_rebuild(tb, kept, lane, [&](int s) { return spos[lane][s]; }, [&](int s) { return sang[lane][s]; });
+  if (!held) {
+    *reinterpret_cast<unsigned*>(SF_CHUNK(misc, 0) + 16u * lane + 8u) = kept | (wp << SF_MPOOL_SHIFT);
+    return;
+  }
+  // the held lane's chunks into the stash, eight pieces in flight at a time (as sf_lanes_load_kernel moves them)
+  u4_t base[kLsShell];
+#pragma unroll
+  for (int p = kLsBase; p < kLsShell; p++) base[p] = *hold_chunk(tb, p, lane);
+#pragma unroll
+  for (int p = kLsBase; p < kLsShell; p++) *hold_chunk(sb, p, lane) = base[p];
+  for (int p0 = kLsShell; p0 < kLsMis; p0 += 8) {
+    u4_t v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = *hold_chunk(tb, p0 + j, lane);
+#pragma unroll
+    for (int j = 0; j < 8; j++) *hold_chunk(sb, p0 + j, lane) = v[j];
+  }
+  // ... and the inert game in its place (ship_pos and ship_vel stay)
+  const u4_t tb4 = base[kLsBase + SF_G_timers_b], sc = base[kLsBase + SF_G_score], mi = base[kLsBase + SF_G_misc], sm = base[kLsBase + SF_G_small];
+  *hold_chunk(tb, kLsBase + SF_G_timers_a, lane) = u4_t{0u, 0u, 0u, 0u};
+  *hold_chunk(tb, kLsBase + SF_G_timers_b, lane) = u4_t{0u, tb4.y, tb4.z, tb4.w};
+  *hold_chunk(tb, kLsBase + SF_G_score, lane) = u4_t{sc.x, sc.y, 0u, 0u};
+  *hold_chunk(tb, kLsBase + SF_G_misc, lane) = u4_t{(unsigned)kInertDeath, mi.y & 0xFFFFFFu, wp << SF_MPOOL_SHIFT, 0u};
+  *hold_chunk(tb, kLsBase + SF_G_small, lane) = u4_t{sm.x, sm.y & ~(SF_FL_SHIP_ALIVE << 16), 0u, 0u};
+}
+static_assert((kLsMis - kLsShell) % 8 == 0, "the shell pieces move in rounds of eight");
+
+// Behind the step launch.  The held lanes' chunks come back from the stash; the pool is rebuilt from the active lanes' entries
+// as the tick left them and the held lanes' stashed slots, and its count goes into every lane's missile word.  The held
+// lanes' outputs (each may be null): reward 0, done 0, info 0, ticks 0, event word 0, and the observation row of the
+// restored state (obs_rows_from_stage: sf_lanes_load_kernel's writer; a batch without observation rows gets none).  Their
+// render-hint bits are cleared: a held ship did not die in this call.  No row of a.final_obs is touched.
+__global__ __launch_bounds__(64) void sf_hold_end_kernel(SfKernelArgs a, const uint8_t* active, const unsigned char* stash, void* obs,
+                                                        int32_t* reward, uint8_t* done, uint8_t* info, uint8_t* ticks) {
+  __shared__ d2_t spos[64][SF_NSLOT];
+  __shared__ unsigned short sang[64][SF_NSLOT];
+  __shared__ __attribute__((aligned(16))) unsigned char stage[7 * 1024];  // the held lanes' seven chunks, tile layout (obs)
+  const unsigned lane = threadIdx.x;
+  const long tile_i = blockIdx.x;
+  const long e = tile_i * 64 + lane;
+  const bool held = e < a.n_envs && active[e] == 0;
+  const unsigned long long hmask = __ballot(held);
+  if (hmask == 0ull) return;  // (uniform)
+  unsigned char* const tb = a.state + (size_t)tile_i * sfl::kTileBytes;
+  unsigned char* const sb = const_cast<unsigned char*>(stash) + (size_t)tile_i * sfl::kTileBytes;
+  const unsigned mw = SF_LD(unsigned, SF_CHUNK(misc, 0), 16u * lane + 8u);
+  pool_for_each(tb, (unsigned)__builtin_amdgcn_readfirstlane(mw), lane, [&](unsigned i, unsigned m) {
+    const unsigned ow = SF_MM_OWNER(m);
+    if (!((hmask >> ow) & 1ull)) {  // (an inert lane owns nothing)
+      spos[ow][SF_MM_SLOT(m)] = SF_LD(d2_t, SF_CHUNK(missile_pos, 0), i * 16u);
+      sang[ow][SF_MM_SLOT(m)] = (unsigned short)SF_MM_ANGLE(m);
+    }
+  });
+  unsigned mask = mw & SF_MASK_LOW;
+  if (held) {
+    mask = SF_LD(unsigned, sb, sf_ls_chunk_off(kLsBase + SF_G_misc, lane) + 8u) & SF_MASK_LOW;
+    for (unsigned rest = mask; rest; rest &= rest - 1u) {
+      const unsigned s = (unsigned)__ffs(rest) - 1u;
+      spos[lane][s] = SF_LD(d2_t, sb, sfl::chunk_offset(SF_G_missile_pos, 0) + (size_t)(s * 64u + lane) * 16);
+      sang[lane][s] = (unsigned short)SF_LD(unsigned, sb, sfl::chunk_offset(SF_G_missile_meta, 0) + (size_t)(s * 64u + lane) * 4);
+    }
+  }
+  __syncthreads();
+  const unsigned wp = pool_rebuild(tb, mask, lane, [&](int s) { return spos[lane][s]; }, [&](int s) { return sang[lane][s]; });
+  if (held) {
+    for (int p0 = kLsBase; p0 < kLsMis; p0 += 8) {
+      u4_t v[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) v[j] = p0 + j < kLsMis ? *hold_chunk(sb, p0 + j, lane) : u4_t{0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const int p = p0 + j;
+        if (p >= kLsMis) break;
+        if (p == kLsBase + SF_G_misc) v[j].z = mask | (wp << SF_MPOOL_SHIFT);
+        if (p < kLsShell) *reinterpret_cast<u4_t*>(stage + (p - kLsBase) * 1024 + 16 * lane) = v[j];
+        *hold_chunk(tb, p, lane) = v[j];
+      }
+    }
+    if (reward) reward[e] = 0;
+    if (done) done[e] = 0;
+    if (info) info[e] = 0;
+    if (ticks) ticks[e] = 0;
+    if (a.events) a.events[e] = 0u;
+  } else {
+    *reinterpret_cast<unsigned*>(SF_CHUNK(misc, 0) + 16u * lane + 8u) = mask | (wp << SF_MPOOL_SHIFT);
+    for (int g = 0; g < 7; g++) *reinterpret_cast<u4_t*>(stage + g * 1024 + 16 * lane) = u4_t{0u, 0u, 0u, 0u};  // (defined values below)
+  }
+  if (a.hint && lane == 0) a.hint[tile_i] &= ~hmask;
+  if (obs != nullptr && a.obs_type != 3) obs_rows_from_stage(a, stage, lane, held, obs, (size_t)e);  // (uniform)
+}
+
+// The held lanes' draw records (image batches) from their restored state, behind sf_hold_end_kernel: sf_drawrec_kernel's
+// code for the lanes of the mask's zeros; the active lanes' records are the step launch's own and stay.
+__global__ __launch_bounds__(64) void sf_hold_drawrec_kernel(const unsigned char* state, int n_envs, const uint8_t* active, unsigned char* draw,
+                                                            int pics) {
+  __shared__ unsigned near[64];
+  const long e = (long)blockIdx.x * 64 + threadIdx.x;
+  const unsigned long long hmask = __ballot(e < n_envs && active[e] == 0);
+  if (hmask == 0ull) return;  // (uniform)
+  drawrec_tile(state, n_envs, draw, pics, hmask, near);
+}
+
+hipError_t sf_launch_hold_begin(const SfKernelArgs& a, const uint8_t* active, unsigned char* stash, hipStream_t stream) {
+  hipLaunchKernelGGL(sf_hold_begin_kernel, dim3((unsigned)((a.n_envs + 63) / 64)), dim3(64), 0, stream, a, active, stash);
+  return hipGetLastError();
+}
+
+// ticks [n] = 1: what a plain step launch, which has no ticks output, says of every env in front of sf_hold_end_kernel.  (A
+// kernel, not hipMemsetAsync: as a node of a captured graph the byte memset left other values behind on replay.)
+__global__ __launch_bounds__(kBlock) void sf_hold_one_tick_kernel(uint8_t* ticks, int n) {
+  const long e = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (e < n) ticks[e] = 1;
+}
+
+hipError_t sf_launch_hold_end(const SfKernelArgs& a, const uint8_t* active, const unsigned char* stash, void* obs, int32_t* reward,
+                              uint8_t* done, uint8_t* info, uint8_t* ticks, int one_tick, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.n_envs + 63) / 64));
+  if (one_tick && ticks)
+    hipLaunchKernelGGL(sf_hold_one_tick_kernel, dim3((unsigned)((a.n_envs + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, ticks, a.n_envs);
+  hipLaunchKernelGGL(sf_hold_end_kernel, grid, dim3(64), 0, stream, a, active, stash, obs, reward, done, info, ticks);
+  if (a.draw) hipLaunchKernelGGL(sf_hold_drawrec_kernel, grid, dim3(64), 0, stream, a.state, a.n_envs, active, a.draw, a.draw_pics);
   return hipGetLastError();
 }

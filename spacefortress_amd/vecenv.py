@@ -248,6 +248,42 @@ class SFVecEnv:
         self._step_into(actions, at, ptrs, bufs[1], bufs[2], bufs[3], repeat=int(repeat), ticks_out=ticks_out)
         return bufs
 
+    def step_where(self, actions, active, out=None, ticks_out=None):
+        """The masked step (sfmi_hold.h: sf_step_where): the envs whose element of `active` (bool or uint8 device tensor [N],
+        any non-zero byte) is set play `actions` for `self.frame_skip` ticks exactly as step_tensors would have them play;
+        the others HOLD: not a byte of their state changes (save_lanes rows, counters, spawn stream), they add nothing to
+        episode_stats() and do not touch the final-observation buffer.  Returns (obs, reward, done, info) like step_tensors;
+        a held env reads reward 0, done 0, info 0, the observation (image batches: the frame) of its unchanged state, event
+        word 0, and 0 in `self.last_ticks` (uint8 [N]; `ticks_out` if given), where an active env reads the ticks it played.
+        Which envs are held does not change what the active ones do.  Batches made with auto_reset=False are accepted: hold
+        the finished envs and they stay at their game over while the others play on.  Nothing synchronises and the host never
+        reads the mask; the first call on a batch allocates, later ones can be captured in a graph (with `out`).  ValueError
+        for a mask that is not a contiguous bool / uint8 tensor [N] on this device, during a recording (a replay file holds one
+        action per env and step) and while a duration log or an episode log is enabled (they count rows, not ticks).  The
+        wrappers (FrameStack, SFVecNormalize, DeviceRollout) have no masked form."""
+        n = self.num_envs
+        if not (torch.is_tensor(active) and active.dtype in (torch.uint8, torch.bool) and active.device == self.device
+                and active.dim() == 1 and active.numel() == n and active.is_contiguous()):
+            raise ValueError("step_where: active must be a contiguous uint8 or bool tensor [%d] on %s" % (n, self.device))
+        if self._rec is not None:
+            raise ValueError("step_where() during a recording: a replay file holds one action per env and step, and a held "
+                             "env plays none")
+        if self._durations is not None:
+            raise ValueError("step_where() while a duration log is enabled (enable_durations): the log counts rows, not the "
+                             "ticks an env played")
+        if self._episodes is not None:
+            raise ValueError("step_where() while an episode log is enabled (enable_episode_log): the log counts rows, not the "
+                             "ticks an env played; filter (reward, done, info) by the mask yourself")
+        at = self._act_type(actions)
+        bufs, ptrs = self._outputs(out)
+        ticks = self._ticks_buffer(ticks_out)
+        m = active.view(torch.uint8) if active.dtype == torch.bool else active
+        self._touch()
+        _lib.check(self._L.sf_step_where(self._h, C.c_void_p(m.data_ptr()), C.c_void_p(actions.data_ptr()), at, self.frame_skip,
+                                         ptrs[0], ptrs[1], ptrs[2], ptrs[3], C.c_void_p(ticks.data_ptr()), self._stream()))
+        self.last_ticks = ticks
+        return bufs
+
     def _act_type(self, actions, rows=False):
         """THE check of an action tensor in front of a launch: contiguous, on this device, [N] (rows: [K, N]), uint8 / int32 /
         int64.  Returns the C ABI's act type."""
