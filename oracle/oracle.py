@@ -109,8 +109,56 @@ def oracle_lib():
         L.sfo_env_replay.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
         L.sfo_srand.argtypes = [C.c_void_p, C.c_uint]
         L.sfo_rand.argtypes = [C.c_void_p]
+        L.sfo_event_name.restype = C.c_char_p
+        L.sfo_event_name.argtypes = [C.c_int]
+        L.sfo_game_events.restype = C.c_uint32
+        L.sfo_game_events.argtypes = [C.c_void_p]
+        L.sfo_env_events.restype = C.c_uint32
+        L.sfo_env_events.argtypes = [C.c_void_p]
+        L.sfo_vec_events.argtypes = [C.c_void_p, C.c_void_p]
         _oracle = L
     return _oracle
+
+
+KEY_EVENT_NAMES = tuple(p + k for p in ("press-", "release-") for k in ("fire", "thrust", "left", "right"))
+OWN_EVENT_NAMES = ("missile-left", "game-over")  # the project's two bits (include/sfmi.h): the reference has no string for them
+
+_event_bits = None
+
+
+def event_names():
+    """The oracle's event names, by ITS bit (sf_oracle.h SFO_EV_*: the order of the reference's call sites)."""
+    L = oracle_lib()
+    return [L.sfo_event_name(i).decode() for i in range(L.sfo_event_count())]
+
+
+def names_of_oracle_word(w):
+    """An oracle event word (SFO_EV_* bits) as the set of its names."""
+    return {nm for i, nm in enumerate(event_names()) if (int(w) >> i) & 1}
+
+
+def to_sf_events(words):
+    """Oracle event words -> SF_EV_* words (include/sfmi.h), BY NAME through spacefortress_amd._lib.EVENT_NAMES: the two
+    enumerations are in different orders on purpose, so a bit transposed between sfmi.h and _lib does not cancel out."""
+    global _event_bits
+    if _event_bits is None:
+        from spacefortress_amd._lib import EVENT_NAMES
+
+        bit_of = {nm: b for b, nm in EVENT_NAMES.items()}
+        assert len(bit_of) == len(EVENT_NAMES) and sorted(bit_of) == sorted(event_names()), (sorted(bit_of), event_names())
+        _event_bits = np.array([bit_of[nm] for nm in event_names()], np.uint32)
+    w = np.asarray(words, np.uint32)
+    out = np.zeros(w.shape, np.uint32)
+    for i, b in enumerate(_event_bits):
+        out |= np.where((w >> np.uint32(i)) & np.uint32(1), b, np.uint32(0)).astype(np.uint32)
+    return out
+
+
+def names_of_sf_word(w):
+    """An SF_EV_* word (the device's, or to_sf_events') as the set of its names."""
+    from spacefortress_amd._lib import EVENT_NAMES
+
+    return {nm for b, nm in EVENT_NAMES.items() if int(w) & b}
 
 
 def have_ref():
@@ -130,6 +178,7 @@ def ref_lib():
         L.sfref_step_one_tick.argtypes = [C.c_void_p, C.c_int]
         L.sfref_is_game_over.argtypes = [C.c_void_p]
         L.sfref_snapshot.argtypes = [C.c_void_p, C.c_void_p]
+        L.sfref_load_snapshot.argtypes = [C.c_void_p, C.c_void_p]
         L.sfref_hex_points.argtypes = [C.c_void_p, C.c_void_p]
         L.sfref_replay.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sfref_rollout.restype = C.c_long
@@ -243,6 +292,19 @@ class OracleEnv(_GameApi):
         self.L.sfo_env_snapshot(self.h, _ptr(s))
         return s
 
+    def load_snapshot(self, snap, prev_vlner=0):
+        s = np.ascontiguousarray(snap, SNAPSHOT_DTYPE).reshape(())
+        self.L.sfo_env_load_snapshot(self.h, _ptr(s), int(prev_vlner))
+
+    def event_names(self, engine=False):
+        """The names of the last tick's events: of the last step() (a finishing tick's own, game-over included), or with
+        `engine` of the last step_one_tick()."""
+        return names_of_oracle_word(self.L.sfo_game_events(self.g) if engine else self.L.sfo_env_events(self.h))
+
+    def events(self, engine=False):
+        """The same as one SF_EV_* word (include/sfmi.h), translated by name."""
+        return int(to_sf_events(self.L.sfo_game_events(self.g) if engine else self.L.sfo_env_events(self.h)))
+
     def rollout(self, n_steps, lcg_seed):
         return self.L.sfo_rollout(self.h, n_steps, lcg_seed)
 
@@ -315,6 +377,13 @@ class OracleVecEnv:
     def prev_vlner(self):
         return np.array([self.L.sfo_vec_prev_vlner(self.h, i) for i in range(self.n)], np.int32)
 
+    def events(self):
+        """uint32 [n]: every env's SF_EV_* word (include/sfmi.h, translated by name) of the last step(); a finishing tick's
+        word is that tick's, game-over included, not the new game's."""
+        w = np.zeros(self.n, np.uint32)
+        self.L.sfo_vec_events(self.h, _ptr(w))
+        return to_sf_events(w)
+
     def load_snapshots(self, snaps, prev_vlner=None):
         """Put every env into a constructed state (snaps: SNAPSHOT_DTYPE[n])."""
         snaps = np.ascontiguousarray(snaps, SNAPSHOT_DTYPE)
@@ -358,6 +427,11 @@ class RefGame(_GameApi):
         s = np.zeros((), SNAPSHOT_DTYPE)
         self.L.sfref_snapshot(self.h, _ptr(s))
         return s
+
+    def load_snapshot(self, snap):
+        """Put the reference's own game into a constructed state (sfref_load_snapshot: every member the snapshot carries)."""
+        s = np.ascontiguousarray(snap, SNAPSHOT_DTYPE).reshape(())
+        self.L.sfref_load_snapshot(self.h, _ptr(s))
 
     def rollout(self, n_steps, lcg_seed):
         return self.L.sfref_rollout(self.h, n_steps, lcg_seed)

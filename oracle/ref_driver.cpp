@@ -272,7 +272,8 @@ long sfref_rollout(void* h, long n_steps, unsigned lcg_seed) {
 
 }  // extern "C"
 
-/* Write a snapshot INTO the reference game (its members are public): every field sfref_snapshot reads.
+/* Write a snapshot INTO the reference game (its members are public): every field sfref_snapshot reads but the extras and
+ * the collision flags, which the next tick computes anew.
  * Lets the fixtures place the reference's own objects anywhere (a ship at every heading, crowded pools). */
 extern "C" void sfref_load_snapshot(void* h, const sfo_snapshot* s) {
   Game* g = ((RefGame*)h)->game;
@@ -285,6 +286,30 @@ extern "C" void sfref_load_snapshot(void* h, const sfo_snapshot* s) {
   g->mShip.mVel.mY = s->ship_vy;
   g->mShip.mAngle = s->ship_angle;
   g->mShip.mDeathTimer = s->ship_death_timer;
+  /* the key state and the statistics, so that a loaded game can be PLAYED on in step with the oracle (the renderer reads
+   * none of them) */
+  g->mShip.mFireTimer = s->fire_timer;
+  g->mShip.mThrustTimer = s->thrust_timer;
+  g->mShip.mLeftTimer = s->left_timer;
+  g->mShip.mRightTimer = s->right_timer;
+  g->mShip.mThrustFlag = s->thrust_flag;
+  g->mShip.mFireFlag = s->fire_flag;
+  g->mShip.mLeftFlag = s->left_flag;
+  g->mShip.mRightFlag = s->right_flag;
+  g->mShip.mTurnFlag = (Turn)s->turn_flag;
+  g->mStats.bigHexDeaths = s->stats[0];
+  g->mStats.smallHexDeaths = s->stats[1];
+  g->mStats.shellDeaths = s->stats[2];
+  g->mStats.shipDeaths = s->stats[3];
+  g->mStats.resets = s->stats[4];
+  g->mStats.destroyedFortresses = s->stats[5];
+  g->mStats.missedShots = s->stats[6];
+  g->mStats.totalShots = s->stats[7];
+  g->mStats.totalThrusts = s->stats[8];
+  g->mStats.totalLefts = s->stats[9];
+  g->mStats.totalRights = s->stats[10];
+  g->mStats.vlnerIncs = s->stats[11];
+  g->mStats.maxVlner = s->stats[12];
   g->mFortress.mAlive = s->fort_alive;
   g->mFortress.mAngle = s->fort_angle;
   g->mFortress.mLastAngle = s->fort_last_angle;
@@ -301,6 +326,8 @@ extern "C" void sfref_load_snapshot(void* h, const sfo_snapshot* s) {
     g->mMissiles[i].mVel.mX = s->missile_vx[i];
     g->mMissiles[i].mVel.mY = s->missile_vy[i];
     g->mMissiles[i].mAngle = s->missile_angle[i];
+    /* (the engine gives a projectile its collision radius when it is fired, SRC/game.cpp:163,180: a loaded one gets it here) */
+    g->mMissiles[i].mCollisionRadius = ((RefGame*)h)->cfg->getInt("missileCollisionRadius");
   }
   for (int i = 0; i < MAX_SHELLS; i++) {
     g->mShells[i].mAlive = s->shell_alive[i];
@@ -309,6 +336,7 @@ extern "C" void sfref_load_snapshot(void* h, const sfo_snapshot* s) {
     g->mShells[i].mVel.mX = s->shell_vx[i];
     g->mShells[i].mVel.mY = s->shell_vy[i];
     g->mShells[i].mAngle = s->shell_angle[i];
+    g->mShells[i].mCollisionRadius = ((RefGame*)h)->cfg->getInt("shellCollisionRadius");
   }
 }
 

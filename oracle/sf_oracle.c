@@ -180,6 +180,19 @@ static void game_reward(sfo_game* g, float amount) { /* :97-102 */
 
 static void game_penalize(sfo_game* g, float amount) { game_reward(g, -amount); } /* :104-106 */
 
+/* The tick's events as one word: a bit per string Game::addEvent is given (:124-127), set where the reference makes the
+ * call, at the place this file restates the code around it -- inside update_missiles per missile of the slot-order walk,
+ * never from the statistics.  The word keeps no order and no multiplicity.  Bit i is SFO_EV_* of sf_oracle.h, an
+ * enumeration of this file's own in the order of the reference's call sites; callers go through the NAMES. */
+static const char* const k_event_names[SFO_EV_COUNT] = {
+    "ship-respawn", "fortress-fired", "missile-fired", "fortress-respawn",
+    "press-fire", "press-thrust", "press-left", "press-right",
+    "release-fire", "release-thrust", "release-left", "release-right",
+    "explode-bighex", "explode-smallhex", "hit-fortress", "vlner-increased", "fortress-destroyed", "vlner-reset",
+    "hit-dead-fortress", "shell-hit-ship", "missile-left", "game-over"};
+
+static void add_event(sfo_game* g, int ev) { g->event_word |= 1u << ev; } /* :124-127 */
+
 static void maybe_reset_key_events(sfo_game* g) { /* :90-95 */
   if (g->events_processed) {
     g->n_events = 0;
@@ -220,6 +233,7 @@ static void monitor_ship_respawn(sfo_game* g) { /* :151-157 */
   if (!g->ship.alive && g->ship_death_timer >= g->cfg.explode_duration) {
     reset_ship(g);
     g->fort_timer = 0;
+    add_event(g, SFO_EV_SHIP_RESPAWN); /* :155 */
   }
 }
 
@@ -234,6 +248,7 @@ static void fire_shell(sfo_game* g, const sfo_vec* p, double angle) { /* :159-17
       s->angle = angle;
       s->vel.x = g->cfg.shell_speed * cos(deg2rad(angle));
       s->vel.y = g->cfg.shell_speed * sin(deg2rad(angle));
+      add_event(g, SFO_EV_FORTRESS_FIRED); /* :169 */
       return;
     }
   }
@@ -251,6 +266,7 @@ static void fire_missile(sfo_game* g, const sfo_vec* p, double angle) { /* :175-
       m->angle = angle;
       m->vel.x = g->cfg.missile_speed * cos(deg2rad(angle));
       m->vel.y = g->cfg.missile_speed * sin(deg2rad(angle));
+      add_event(g, SFO_EV_MISSILE_FIRED); /* :186 */
       game_penalize(g, (float)g->cfg.missile_penalty);
       return;
     }
@@ -265,6 +281,7 @@ static void update_fortress(sfo_game* g) { /* :194-216 */
   if (!g->fortress.alive && g->fort_death_timer > 1000) {
     g->fort_timer = 0;
     g->fortress.alive = 1;
+    add_event(g, SFO_EV_FORTRESS_RESPAWN); /* :202 */
   }
   if (g->ship.alive) {
     g->fortress.angle = std_angle(ceil(angle_to_ship / g->cfg.sector_size) * g->cfg.sector_size);
@@ -279,6 +296,9 @@ static void update_fortress(sfo_game* g) { /* :194-216 */
   }
 }
 
+/* :223 logs every press/release CALL ("release-thrust" on each tick the wrapper holds the key up, ENV:213-229).  The word's
+ * eight key bits are the key STATE CHANGES of the tick instead, what include/sfmi.h documents: they are set in the
+ * branches below that flip a flag, a subset of the reference's strings. */
 static void process_key_state(sfo_game* g) { /* :218-272 */
   int i;
   maybe_reset_key_events(g);
@@ -286,18 +306,22 @@ static void process_key_state(sfo_game* g) { /* :218-272 */
     int sym = g->events[i].sym;
     if (g->events[i].state) {
       if (sym == SFO_LEFT_KEY && !g->left_flag) {
+        add_event(g, SFO_EV_PRESS_FIRE + 2);
         g->left_flag = 1;
         g->left_timer = 0;
         g->stats.total_lefts += 1;
       } else if (sym == SFO_RIGHT_KEY && !g->right_flag) {
+        add_event(g, SFO_EV_PRESS_FIRE + 3);
         g->right_flag = 1;
         g->right_timer = 0;
         g->stats.total_rights += 1;
       } else if (sym == SFO_THRUST_KEY && !g->thrust_flag) {
+        add_event(g, SFO_EV_PRESS_FIRE + 1);
         g->thrust_flag = 1;
         g->thrust_timer = 0;
         g->stats.total_thrusts += 1;
       } else if (sym == SFO_FIRE_KEY && !g->fire_flag) {
+        add_event(g, SFO_EV_PRESS_FIRE);
         fire_missile(g, &g->ship.pos, g->ship.angle);
         g->fire_flag = 1;
         /* :240-243 shot-interval telemetry: not on the step outputs */
@@ -306,15 +330,19 @@ static void process_key_state(sfo_game* g) { /* :218-272 */
       }
     } else {
       if (sym == SFO_LEFT_KEY && g->left_flag) {
+        add_event(g, SFO_EV_RELEASE_FIRE + 2);
         g->left_flag = 0;
         g->left_timer = 0;
       } else if (sym == SFO_RIGHT_KEY && g->right_flag) {
+        add_event(g, SFO_EV_RELEASE_FIRE + 3);
         g->right_flag = 0;
         g->right_timer = 0;
       } else if (sym == SFO_THRUST_KEY && g->thrust_flag) {
+        add_event(g, SFO_EV_RELEASE_FIRE + 1);
         g->thrust_flag = 0;
         g->thrust_timer = 0;
       } else if (sym == SFO_FIRE_KEY && g->fire_flag) {
+        add_event(g, SFO_EV_RELEASE_FIRE);
         g->fire_flag = 0;
         g->fire_timer = 0;
       }
@@ -391,11 +419,13 @@ static void update_ship(sfo_game* g) { /* :314-351 */
     game_penalize(g, (float)g->cfg.ship_death_penalty);
     g->stats.big_hex_deaths += 1;
     g->col_big_hex = 1;
+    add_event(g, SFO_EV_EXPLODE_BIGHEX); /* :342 */
   } else if (hex_inside(g->small_hex, &g->ship.pos)) {
     kill_ship(g);
     game_penalize(g, (float)g->cfg.ship_death_penalty);
     g->stats.small_hex_deaths += 1;
     g->col_small_hex = 1;
+    add_event(g, SFO_EV_EXPLODE_SMALLHEX); /* :348 */
   }
 }
 
@@ -410,27 +440,34 @@ static void update_missiles(sfo_game* g) { /* :353-402 */
       m->alive = 0;
       g->col_missile_fortress = 1;
       if (g->fortress.alive) {
+        add_event(g, SFO_EV_HIT_FORTRESS); /* :363 */
         if (g->fort_vuln_timer >= g->cfg.vuln_time) {
           g->vlner += 1;
           g->stats.vlner_incs += 1;
           if (g->vlner > g->stats.max_vlner) g->stats.max_vlner = g->vlner;
+          add_event(g, SFO_EV_VLNER_INCREASED); /* :371 */
         } else {
           if (g->vlner >= g->cfg.vuln_threshold + 1) {
             g->fortress.alive = 0;
             g->fort_death_timer = 0;
             game_reward(g, (float)(g->cfg.destroy_fortress + 0 /* mDestroyFortressExtraPoints, :47 */));
+            add_event(g, SFO_EV_FORTRESS_DESTROYED); /* :381 */
             g->stats.destroyed_fortresses += 1;
           } else {
+            add_event(g, SFO_EV_VLNER_RESET); /* :385 */
             g->stats.resets += 1;
           }
           g->vlner = 0;
         }
         g->fort_vuln_timer = 0;
+      } else {
+        add_event(g, SFO_EV_HIT_DEAD_FORTRESS); /* :393 */
       }
     } else if (outside_game_area(g, &m->pos)) {
       m->alive = 0;
       game_penalize(g, (float)g->cfg.miss_penalty);
       g->stats.missed_shots += 1;
+      add_event(g, SFO_EV_MISSILE_LEFT); /* the project's own bit (include/sfmi.h): the reference has no string here */
     }
   }
 }
@@ -448,6 +485,7 @@ static void update_shells(sfo_game* g) { /* :404-423 */
       kill_ship(g);
       game_penalize(g, (float)g->cfg.ship_death_penalty);
       g->stats.shell_deaths += 1;
+      add_event(g, SFO_EV_SHELL_HIT_SHIP); /* :417 */
     } else if (outside_game_area(g, &s->pos)) {
       s->alive = 0;
     }
@@ -468,6 +506,7 @@ static void step_timers(sfo_game* g, int ms) { /* :425-451 */
 
 static void reset_tick(sfo_game* g) { /* :453-467 */
   g->col_big_hex = g->col_small_hex = g->col_missile_fortress = g->col_shell_ship = 0;
+  g->event_word = 0; /* resetEvents, :460-462 */
 }
 
 void sfo_game_init(sfo_game* g, const sfo_config* cfg, sfo_rng* rng) { /* :18-82 */
@@ -505,6 +544,8 @@ int sfo_step_one_tick(sfo_game* g, int ms) { /* :473-485 */
   update_shells(g);
   update_missiles(g);
   step_timers(g, ms);
+  /* the project's own bit (include/sfmi.h): isGameOver() (:487-489) holds as this tick ends */
+  if (sfo_is_game_over(g)) add_event(g, SFO_EV_GAME_OVER);
   return (int)g->reward; /* float -> int truncation, decl SRC/game.hh:138 */
 }
 
@@ -777,6 +818,7 @@ int sfo_env_step(sfo_env* e, int action, double* obs, int* reward, int* done, in
     e->prev_vlner = e->g.vlner;
   }
   *reward = r;
+  e->last_events = e->g.event_word; /* kept here: the vec-env worker's reset makes a new Game, whose word is empty */
   *done = sfo_is_game_over(&e->g); /* ENV:246 */
   *info = fort_kill;               /* ENV:253: info is the bare bool */
   if (obs) sfo_env_features(e, obs);
@@ -896,6 +938,16 @@ sfo_game* sfo_env_game(sfo_env* e) { return &e->g; }
 int sfo_env_n_actions(const sfo_env* e) { return e->n_actions; }
 int sfo_env_action_keys(const sfo_env* e, int a) { return e->action_keys[a]; }
 int sfo_env_prev_vlner(const sfo_env* e) { return e->prev_vlner; }
+int sfo_event_count(void) { return SFO_EV_COUNT; }
+const char* sfo_event_name(int bit) { return bit >= 0 && bit < SFO_EV_COUNT ? k_event_names[bit] : NULL; }
+/* the word of the last tick played: of the game as it stands (engine-level calls), of the env's last step (a finishing
+ * tick's word is that tick's, game-over included, whatever reset followed) */
+uint32_t sfo_game_events(const sfo_game* g) { return g->event_word; }
+uint32_t sfo_env_events(const sfo_env* e) { return e->last_events; }
+void sfo_vec_events(sfo_vec_env* v, uint32_t* out) {
+  int i;
+  for (i = 0; i < v->n; i++) out[i] = v->envs[i].last_events;
+}
 void sfo_env_set_faithful_bugs(sfo_env* e, int on) { e->faithful_bugs = on; }
 void sfo_env_set_ref_reset_obs(sfo_env* e, int on) { e->ref_reset_obs = on; }
 void sfo_env_snapshot(const sfo_env* e, sfo_snapshot* s) { sfo_game_snapshot(&e->g, s); }

@@ -35,6 +35,20 @@ enum { SFO_NO_KEY = 0, SFO_FIRE_KEY = 1, SFO_THRUST_KEY = 2, SFO_LEFT_KEY = 3, S
 /* SRC/game.hh:13 */
 enum { SFO_NO_TURN = 0, SFO_TURN_LEFT = 1, SFO_TURN_RIGHT = 2 };
 
+/* The tick's event word: one bit per string the reference hands Game::addEvent, in the order of its call sites
+ * (SRC/game.cpp:155,169,186,202,223,342,348,363,371,381,385,393,417), then the project's two own bits (include/sfmi.h).
+ * This order is the oracle's alone, NOT sfmi.h's SF_EV_*: users translate through sfo_event_name(). */
+enum {
+  SFO_EV_SHIP_RESPAWN = 0, SFO_EV_FORTRESS_FIRED, SFO_EV_MISSILE_FIRED, SFO_EV_FORTRESS_RESPAWN,
+  SFO_EV_PRESS_FIRE, SFO_EV_PRESS_THRUST, SFO_EV_PRESS_LEFT, SFO_EV_PRESS_RIGHT,
+  SFO_EV_RELEASE_FIRE, SFO_EV_RELEASE_THRUST, SFO_EV_RELEASE_LEFT, SFO_EV_RELEASE_RIGHT,
+  SFO_EV_EXPLODE_BIGHEX, SFO_EV_EXPLODE_SMALLHEX, SFO_EV_HIT_FORTRESS, SFO_EV_VLNER_INCREASED,
+  SFO_EV_FORTRESS_DESTROYED, SFO_EV_VLNER_RESET, SFO_EV_HIT_DEAD_FORTRESS, SFO_EV_SHELL_HIT_SHIP,
+  SFO_EV_MISSILE_LEFT, /* a missile left the game area: where Stats.missedShots is counted */
+  SFO_EV_GAME_OVER,    /* isGameOver() holds at the end of the tick */
+  SFO_EV_COUNT
+};
+
 /* The preset values the path reads (SRC/configs.cpp:3-89); the string-keyed
  * map of SRC/config.cpp is not reproduced. */
 typedef struct {
@@ -105,6 +119,7 @@ typedef struct {
   float points, raw_points;
   int vlner;
   float reward;
+  uint32_t event_word; /* mEvents (SRC/game.hh) as bits SFO_EV_*: cleared by reset_tick, set by add_event */
 } sfo_game;
 
 /* --- RNG (glibc srandom_r / random_r TYPE_3) --- */
@@ -141,6 +156,7 @@ typedef struct {
   int pb_width, pb_height; /* ENV:57-58 -> 90, 92 (normalized-features divisor) */
   int ref_reset_obs;    /* 1: a new Game's mExtra reads 0, 0, 0 until its first tick -- what the reference's reset() returns on
                            fresh memory (SRC/game.cpp:78 leaves it unwritten; ENV:163-178); 0: computeExtra(spawn state) */
+  uint32_t last_events; /* the event word of the last sfo_env_step's tick: survives the reset that follows a finishing tick */
 } sfo_env;
 
 /* action_set follows ENV:67-89 (1 = reduced set, 0/-1 = all key combinations) */
@@ -202,6 +218,11 @@ sfo_game* sfo_env_game(sfo_env* e);
 int sfo_env_n_actions(const sfo_env* e);
 int sfo_env_action_keys(const sfo_env* e, int a);
 int sfo_env_prev_vlner(const sfo_env* e);
+int sfo_event_count(void);
+const char* sfo_event_name(int bit); /* the reference's string of bit SFO_EV_* ("missile-left", "game-over" for the two own bits) */
+uint32_t sfo_game_events(const sfo_game* g); /* the last tick's word of a game stepped at engine level */
+uint32_t sfo_env_events(const sfo_env* e);   /* the word of the last sfo_env_step */
+void sfo_vec_events(sfo_vec_env* v, uint32_t* out /* [n] */); /* the words of the last sfo_vec_step */
 void sfo_env_set_faithful_bugs(sfo_env* e, int on);
 void sfo_env_set_ref_reset_obs(sfo_env* e, int on); /* takes effect at the next reset */
 void sfo_env_snapshot(const sfo_env* e, sfo_snapshot* s);

@@ -6,8 +6,9 @@ oracle's.  One copy of what the step kernel's test files used to carry each:
   * the state builders `fresh`, `fuzz_sparse` and `fuzz_crowded` (two fuzzers that draw in different orders: the tests'
     oracle-side event assertions hold for the states each of them makes, so they stay two);
   * `load_state` / `load_both`, `oracle_ticks` / `oracle_trace`;
-  * `play`, the device's half: it steps a batch through [T, N] actions and never touches the oracle;
-  * `check_ticks`, the comparing half: numpy only, so it runs without a GPU (tests/test_lockstep_model.py holds it to
+  * `play`, the device's half: it steps a batch through [T, N] actions and never touches the oracle; asked to, it switches
+    the event words on (sfmi.h SF_EV_*) and brings back every tick's;
+  * `check_ticks`, the comparing half (the event words, where play() brought them, bit for bit): numpy only, so it runs without a GPU (tests/test_lockstep_model.py holds it to
     account there), and `same_bytes` for two batches that must agree byte for byte.
 
 Nothing here decides WHAT a test compares: the observation rule and the ticks at which the state is fetched are arguments,
@@ -180,12 +181,14 @@ def load_state(env, base, pv=None, extra=None):
         env.set_field(k, v)
 
 
-def make_env(sfa, gametype, base, pv=None, extra=None, f64=False, **kw):
-    """A features batch (float32 rows, or float64) in the state `base`."""
+def make_env(sfa, gametype, base, pv=None, extra=None, f64=False, events=False, **kw):
+    """A features batch (float32 rows, or float64) in the state `base`; `events`: with its event words switched on."""
     import torch
 
     env = sfa.SFVecEnv(len(base), gametype=gametype, obs_dtype=torch.float64 if f64 else torch.float32, **kw)
     load_state(env, base, pv, extra)
+    if events:
+        env.enable_events()
     return env
 
 
@@ -206,15 +209,16 @@ def load_both(sfa, O, gametype, snaps, prev_vlner=None, **kw):
 
 def oracle_ticks(orc, acts, snap_at=None):
     """Step `orc` through acts [T, n]; yields per tick (obs float64, reward, done, info, snapshots after the tick -- None
-    where `snap_at(t)` is false; every tick by default).  A generator: a long run is compared tick by tick, not stored."""
+    where `snap_at(t)` is false; every tick by default --, the tick's event words uint32 [n] as SF_EV_* bits).  A generator:
+    a long run is compared tick by tick, not stored."""
     for t in range(len(acts)):
         out = orc.step(np.asarray(acts[t]).astype(np.int32))
-        yield out + (orc.snapshots() if snap_at is None or snap_at(t) else None,)
+        yield out + (orc.snapshots() if snap_at is None or snap_at(t) else None, orc.events())
 
 
 def oracle_trace(O, gametype, base, pv, acts, lanes=None, real_shell_count=False):
     """The oracle's side of a lock-step from the state `base` (of `lanes` of it, or of all): per tick (obs float64, reward,
-    done, info, snapshots after the tick)."""
+    done, info, snapshots after the tick, event words)."""
     if lanes is not None:
         base, pv, acts = base[lanes], np.asarray(pv)[lanes], np.asarray(acts)[:, lanes]
     orc = O.OracleVecEnv(gametype, len(base))
@@ -227,12 +231,13 @@ def oracle_trace(O, gametype, base, pv, acts, lanes=None, real_shell_count=False
 
 # ---------------------------------------------------------------- the device's half
 
-Ticks = namedtuple("Ticks", "obs reward done info played states")
+Ticks = namedtuple("Ticks", "obs reward done info played states events", defaults=(None,))
 Ticks.__doc__ = """What play() returns: obs [T, N, D], reward int32 [T, N], done and info uint8 [T, N] as the launch wrote them,
-the actions played uint8 [T, N], and {tick: state_dict() after that tick}."""
+the actions played uint8 [T, N], {tick: state_dict() after that tick}, and -- where play() was asked for them -- the event
+words uint32 [T, N] (sfmi.h SF_EV_*), else None."""
 
 
-def play(env, acts, mode, state_at, out=None, before=None, check_state=False):
+def play(env, acts, mode, state_at, out=None, before=None, check_state=False, events=False):
     """Step `env` through acts [T, N] (uint8) and return Ticks; the oracle is not touched.
       mode "step"     one step_tensors per tick;
            "sampled"  one step_sampled per tick: the lanes draw their own actions, `acts` gives only T, and Ticks.played is
@@ -242,6 +247,8 @@ def play(env, acts, mode, state_at, out=None, before=None, check_state=False):
     The outputs are written into [T, N] tensors made up front and fetched once at the end: no host round trip per tick
     but the state fetches asked for.  `out`: the four tensors every step is to write into (a caller's arena), copied from
     on the device.  `before(env)`: called right in front of the first launch, behind every upload and allocation.
+    `events`: enable_events() first, and return the words of every tick: `env.events` copied on the device after each
+    single step, `env.rollout_events` of a fused launch.
     Ends with check_actions(), and with check_state() if asked."""
     import torch
 
@@ -250,11 +257,17 @@ def play(env, acts, mode, state_at, out=None, before=None, check_state=False):
     want = state_at if state_at is not None else (lambda t: False)
     a = torch.from_numpy(np.array(acts)).to(dev)  # (a copy: a shared case's actions are read-only)
     states = {}
+    ev = None
+    if events:
+        env.enable_events()
     if mode == "fused":
         assert out is None and not any(want(t) for t in range(T - 1)), "a fused launch leaves only its last tick's state"
         if before is not None:
             before(env)
         obs, rew, done, info = env.rollout(a)
+        if events:
+            ev = env.rollout_events
+            assert tuple(ev.shape) == (T, N), tuple(ev.shape)
         if want(T - 1):
             states[T - 1] = env.state_dict()
         played = a
@@ -265,6 +278,8 @@ def play(env, acts, mode, state_at, out=None, before=None, check_state=False):
         done = torch.empty((T, N), dtype=torch.uint8, device=dev)
         info = torch.empty((T, N), dtype=torch.uint8, device=dev)
         played = torch.empty((T, N), dtype=torch.uint8, device=dev) if mode == "sampled" else a
+        if events:
+            ev = torch.empty((T, N), dtype=torch.int32, device=dev)
         if before is not None:
             before(env)
         for t in range(T):
@@ -276,6 +291,8 @@ def play(env, acts, mode, state_at, out=None, before=None, check_state=False):
             if out is not None:
                 for dst, src in zip((obs[t], rew[t], done[t], info[t]), out):
                     dst.copy_(src)
+            if events:
+                ev[t].copy_(env.events)
             if want(t):
                 states[t] = env.state_dict()
     if dev.type == "cuda":
@@ -283,7 +300,8 @@ def play(env, acts, mode, state_at, out=None, before=None, check_state=False):
     env.check_actions()
     if check_state:
         env.check_state()
-    return Ticks(*(x.cpu().numpy() for x in (obs, rew, done, info, played)), states)
+    return Ticks(*(x.cpu().numpy() for x in (obs, rew, done, info, played)), states,
+                 None if ev is None else ev.cpu().numpy().view(np.uint32))
 
 
 def run_device(env, acts_tn):
@@ -294,6 +312,13 @@ def run_device(env, acts_tn):
 
 
 # ---------------------------------------------------------------- the comparison
+
+def event_names(word):
+    """An SF_EV_* word as the set of its names (spacefortress_amd._lib.EVENT_NAMES)."""
+    from spacefortress_amd._lib import EVENT_NAMES
+
+    return {nm for b, nm in EVENT_NAMES.items() if int(word) & b}
+
 
 def _f32_bits(a, b):
     assert a.dtype == np.float32, a.dtype
@@ -314,14 +339,16 @@ OBS_RULES = {
 
 
 def check_ticks(ticks, trace, obs_rule, lanes=None):
-    """Hold what play() returned to the oracle's `trace` (a list or a generator of (obs, reward, done, info, snapshots) per
-    tick; of `lanes` of the batch, or of all of it): reward / done / info exactly, observations by `obs_rule` (a name of
-    OBS_RULES, or a callable like them), and every state in ticks.states through sfcompare.compare_state.  Raises
-    AssertionError with the tick and the first offending indices."""
+    """Hold what play() returned to the oracle's `trace` (a list or a generator of (obs, reward, done, info, snapshots, event
+    words) per tick; of `lanes` of the batch, or of all of it): reward / done / info exactly, observations by `obs_rule` (a
+    name of OBS_RULES, or a callable like them), every state in ticks.states through sfcompare.compare_state, and -- whenever
+    ticks.events is there -- the event words exactly, every bit of every lane.  Raises AssertionError with the tick and the
+    first offending indices (event words: the lanes, and per lane the names the batch has and the names the oracle has)."""
     rule = OBS_RULES[obs_rule] if isinstance(obs_rule, str) else obs_rule
     sel = slice(None) if lanes is None else lanes
     T = 0
-    for t, (oo, orw, od, oi, snaps) in enumerate(trace):
+    for t, tr in enumerate(trace):
+        oo, orw, od, oi, snaps = tr[:5]
         obs, rew, done, info = ticks.obs[t][sel], ticks.reward[t][sel], ticks.done[t][sel], ticks.info[t][sel]
         bad = np.argwhere(~rule(obs, oo))
         assert bad.size == 0, (t, "obs", bad[:5].tolist(), obs[bad[0][0]].tolist(), oo[bad[0][0]].tolist())
@@ -332,6 +359,13 @@ def check_ticks(ticks, trace, obs_rule, lanes=None):
             assert snaps is not None, (t, "the trace has no snapshots for a tick whose state was fetched")
             bad = compare_state(ticks.states[t], snaps, lanes=lanes)
             assert not bad, (t, "state", bad)
+        if ticks.events is not None:
+            assert len(tr) > 5 and tr[5] is not None, (t, "the trace has no event words")
+            got, want = ticks.events[t][sel], np.asarray(tr[5], np.uint32)
+            assert got.dtype == np.uint32 and got.shape == want.shape, (t, "events", got.dtype, got.shape, want.shape)
+            bad = np.flatnonzero(got != want)
+            assert bad.size == 0, (t, "events", bad[:5].tolist(),
+                                   [(sorted(event_names(got[i])), sorted(event_names(want[i]))) for i in bad[:5]])
         T = t + 1
     assert T == len(ticks.obs), (T, len(ticks.obs))
 
@@ -347,13 +381,14 @@ def every(k):
 
 
 def run_lockstep(sfa, O, gametype, base, pv, acts, launch, state_at, obs_rule, lanes=None, trace=None, extra=None, before=None,
-                 check_state=False, **env_kw):
+                 check_state=False, events=False, **env_kw):
     """The whole of it, for a test with nothing to do in between: a batch in the state `base` plays `acts` through `launch` (a
     name of LAUNCHES), the oracle (of `lanes`, or of all lanes) plays what the batch played -- or `trace` is the oracle's,
-    made beforehand from the same given actions --, and check_ticks compares.  Returns (the oracle's trace, Ticks)."""
+    made beforehand from the same given actions --, and check_ticks compares (`events`: the event words too).  Returns (the
+    oracle's trace, Ticks)."""
     mode, f64 = LAUNCHES[launch]
     env = make_env(sfa, gametype, base, pv, extra, f64, **env_kw)
-    ticks = play(env, acts, mode, state_at, before=before, check_state=check_state)
+    ticks = play(env, acts, mode, state_at, before=before, check_state=check_state, events=events)
     env.close()
     if trace is None:
         trace = oracle_trace(O, gametype, base, pv, ticks.played, lanes, real_shell_count=not env_kw.get("faithful_bugs", True))
@@ -370,13 +405,19 @@ def fused_equals_steps(sfa, gametype, base, pv, acts):
 
 
 def same_bytes(ticks_a, ticks_b):
-    """Two batches that played the same ticks: every output and every fetched state field, byte for byte."""
+    """Two batches that played the same ticks: every output and every fetched state field, byte for byte; the event words
+    too where both have them."""
     for name in ("obs", "reward", "done", "info"):
         x, y = getattr(ticks_a, name), getattr(ticks_b, name)
         assert x.shape == y.shape and x.dtype == y.dtype, (name, x.shape, y.shape, x.dtype, y.dtype)
         if x.tobytes() != y.tobytes():
             bad = np.argwhere(x.view(np.uint8) != y.view(np.uint8))
             raise AssertionError((int(bad[0][0]), name, bad[:5].tolist()))
+    if ticks_a.events is not None and ticks_b.events is not None:  # (one side without them: events on against events off)
+        x, y = ticks_a.events, ticks_b.events
+        assert x.shape == y.shape and x.dtype == y.dtype, ("events", x.shape, y.shape)
+        bad = np.argwhere(x != y)
+        assert bad.size == 0, (int(bad[0][0]), "events", bad[:5].tolist())
     assert sorted(ticks_a.states) == sorted(ticks_b.states), (sorted(ticks_a.states), sorted(ticks_b.states))
     for t in sorted(ticks_a.states):
         sa, sb = ticks_a.states[t], ticks_b.states[t]

@@ -97,9 +97,10 @@ def _sampled_rule(obs, oo):
 def _census_lockstep(O, env, gametype, base, pv, T, sampled):
     """T ticks of NOOP (sampled: of what the lanes draw, which the oracle then plays) against the oracle, the state after
     every tick; returns (Ticks, the oracle's trace)."""
-    ticks = play(env, np.zeros((T, len(base)), np.uint8), "sampled" if sampled else "step", every(1), check_state=True)
+    ticks = play(env, np.zeros((T, len(base)), np.uint8), "sampled" if sampled else "step", every(1), check_state=True,
+                 events=True)
     trace = oracle_trace(O, gametype, base, pv, ticks.played)
-    for t, (oo, orw, od, oi, snaps) in enumerate(trace):
+    for t, (oo, orw, od, oi, snaps, _) in enumerate(trace):
         sd, rew = ticks.states[t], ticks.reward[t]
         # what the issue names, every lane, exactly ...
         assert np.array_equal((sd["flags"] & 1) != 0, snaps["ship_alive"] != 0), t
@@ -107,7 +108,7 @@ def _census_lockstep(O, env, gametype, base, pv, T, sampled):
             assert np.array_equal(sd["stats"][st], snaps["stats"][:, st]), (t, st)
         assert np.array_equal(rew, orw), (t, np.flatnonzero(rew != orw)[:5])
         assert np.array_equal(sd["ship_death_timer"], snaps["ship_death_timer"]), t
-    # ... and the rest of the tick with it
+    # ... and the rest of the tick with it, the event words included
     check_ticks(ticks, trace, _sampled_rule if sampled else "f32_bits")
     return ticks, trace
 
@@ -216,7 +217,7 @@ def test_full_pool_tick_in_the_last_tile(sfa, oracle_mod, gametype, n):
     O = oracle_mod
     base, last = _full_pool_base(O, gametype, n)
     pv = np.zeros(n, np.int32)
-    env = make_env(sfa, gametype, base, pv)
+    env = make_env(sfa, gametype, base, pv, events=True)
     orc = O.OracleVecEnv(gametype, 64)
     orc.load_snapshots(base[last], pv[last])
     acts = np.zeros((2, n), np.uint8)
@@ -233,6 +234,7 @@ def test_full_pool_tick_in_the_last_tile(sfa, oracle_mod, gametype, n):
         assert bad.size == 0, (t, bad[:5].tolist())
         assert np.array_equal(rew[last], orw) and np.array_equal(done[last].astype(bool), od), t
         assert np.array_equal(info[last].astype(bool), oi), t
+        assert np.array_equal(env.events.cpu().numpy().view(np.uint32)[last], orc.events()), t  # the event words of the last tile
         sd = env.state_dict()
         pool = int(sum(bin(int(m)).count("1") for m in sd["missile_mask"][last]))  # the pool's live entries
         assert pool == int((snaps["missile_alive"] != 0).sum()), (t, pool)

@@ -32,13 +32,13 @@ LOCK, RESPAWN, VULN, TICK = 1000, 1000, 250, 34  # sf_layout.h: lock_time, fort_
 
 def _run(sfa, O, gametype, base, pv, acts, mode="split", lanes=None, extra=None, before=None):
     """Load `base`, play len(acts) ticks (mode "sampled": the lanes draw their own actions, the oracle plays what they drew),
-    compare every tick with the oracle (of `lanes` or of the whole batch): rows rounded to float32 as bit patterns; the state
+    compare every tick with the oracle (of `lanes` or of the whole batch): rows rounded to float32 as bit patterns, the event words bit for bit; the state
     after every tick of a batch of up to 512 envs, else (and of a fused launch) after the last.  `before(env)`: called right
     in front of the first step, for a launch that is to be the second of a pair.  Returns the oracle's trace [(obs, rew,
     done, info, snapshots)] and the device's final state_dict."""
     T = len(acts)
     trace, ticks = run_lockstep(sfa, O, gametype, base, pv, acts, mode, every(1 if (len(base) <= 512 and mode != "fused") else T),
-                                "rounded_f32_bits", lanes=lanes, extra=extra, before=before)
+                                "rounded_f32_bits", lanes=lanes, extra=extra, before=before, events=True)
     return trace, ticks.states[T - 1]
 
 

@@ -5,7 +5,8 @@ leaves with the ship", which these scenarios hold any walk of the slots to (writ
 measured and not kept: profiles/step_outcomes.md).  In lock-step with the CPU oracle, through the harness of
 tests/lockstep.py:
 
-  * observation rows as float32 BIT PATTERNS, reward / done / info exactly, the state through sfcompare.compare_state;
+  * observation rows as float32 BIT PATTERNS, reward / done / info exactly, the state through sfcompare.compare_state, the
+    event word of every lane and tick (sfmi.h SF_EV_*) bit for bit;
   * every scenario asserts, from the ORACLE's trace, that its event happened in the compared tick.
 
 Shapes: 64 and 256 envs (one tile; four tiles in one workgroup), youturn and autoturn, stepped by split launches; the same
@@ -129,7 +130,7 @@ def test_missile_events_of_one_tick(sfa, oracle_mod, gametype, n):
     base, pv, acts = _setup_missile_events(oracle_mod, gametype, n)
     trace = oracle_trace(oracle_mod, gametype, base, pv, acts)
     _events_missile_events(base, trace, n)
-    run_lockstep(sfa, None, gametype, base, pv, acts, "split", every(1), "f32_bits", trace=trace)
+    run_lockstep(sfa, None, gametype, base, pv, acts, "split", every(1), "f32_bits", trace=trace, events=True)
 
 
 # ---------------------------------------------------------------- 2. shells
@@ -231,7 +232,7 @@ def test_shell_outcomes_of_one_tick(sfa, oracle_mod, gametype, n, lone):
     base, pv, acts = _setup_shells(oracle_mod, gametype, n, lone)
     trace = oracle_trace(oracle_mod, gametype, base, pv, acts)
     _events_shells(base, trace, n, lone)
-    run_lockstep(sfa, None, gametype, base, pv, acts, "split", every(1), "f32_bits", trace=trace)
+    run_lockstep(sfa, None, gametype, base, pv, acts, "split", every(1), "f32_bits", trace=trace, events=True)
 
 
 # ---------------------------------------------------------------- 3. the same scenarios through the other launches
@@ -246,7 +247,8 @@ def test_the_scenarios_through_the_other_launches(sfa, oracle_mod, gametype, wha
     setup, events = (_setup_missile_events, _events_missile_events) if what == "missiles" else (_setup_shells, _events_shells)
     base, pv, acts = setup(O, gametype, n)
     # (rows rounded to float32 as bit patterns; the state after every tick, of a fused launch after the last)
-    trace, _ = run_lockstep(sfa, O, gametype, base, pv, acts, mode, every(T if mode == "fused" else 1), "rounded_f32_bits")
+    trace, _ = run_lockstep(sfa, O, gametype, base, pv, acts, mode, every(T if mode == "fused" else 1), "rounded_f32_bits",
+                            events=True)
     events(base, trace, n)
     if mode == "fused":
         fused_equals_steps(sfa, gametype, base, pv, acts)
@@ -282,5 +284,6 @@ def test_three_ticks_of_constructed_states_at_the_larger_shapes(sfa, oracle_mod,
     """128 and 256 envs per workgroup, the split launch with the staggered start (65 536) and the smallest non-split plain
     launch (65 600): a seeded sample of 256 lanes against the oracle, the last tile's among them."""
     base, pv, acts, lanes = _setup_large(oracle_mod, gametype, n)
-    trace, _ = run_lockstep(sfa, oracle_mod, gametype, base, pv, acts, "split", every(len(acts)), "rounded_f32_bits", lanes=lanes)
+    trace, _ = run_lockstep(sfa, oracle_mod, gametype, base, pv, acts, "split", every(len(acts)), "rounded_f32_bits", lanes=lanes,
+                            events=True)
     _events_large(base, trace, lanes)

@@ -33,10 +33,10 @@ SMALL = [64, 256]
 
 def _lockstep(sfa, gametype, base, pv, acts, trace, real_shell_count=False, lanes=None):
     """Load `base` into a float32 features batch (what split launches serve), play `acts`, compare every tick with `trace`
-    (the oracle's, of `lanes` of the batch or of all of it): rows as float32 bit patterns; small batches: the state after
+    (the oracle's, of `lanes` of the batch or of all of it): rows as float32 bit patterns, the event words bit for bit; small batches: the state after
     every tick, the others after the last."""
     run_lockstep(sfa, None, gametype, base, pv, acts, "split", every(1 if len(base) <= 256 else len(acts)), "f32_bits", lanes=lanes,
-                 trace=trace, faithful_bugs=not real_shell_count)
+                 trace=trace, events=True, faithful_bugs=not real_shell_count)
 
 
 # ---------------------------------------------------------------- 1. lanes of one tile finishing on different ticks

@@ -136,15 +136,15 @@ def _batch(O, gametype, n, blocks, T):
 
 def _play(sfa, O, gametype, base, acts, lanes=None):
     """Both batches play `acts`; they are held to each other byte for byte and the first to the oracle (of `lanes` or of all
-    lanes): the state after every tick of a batch of up to 256 envs, else after the first and the last.  Returns the oracle's
+    lanes; the event words of every tick among it): the state after every tick of a batch of up to 256 envs, else after the first and the last.  Returns the oracle's
     trace."""
     n, T = len(base), len(acts)
     pv = np.zeros(n, np.int32)
     e1, e2 = make_env(sfa, gametype, base, pv), make_env(sfa, gametype, base, pv)
     e2.enable_final_obs()  # (the step leaves the split launch: the XTRA / FOBS instantiation, the same outputs)
     state_at = lambda t: n <= 256 or t in (0, T - 1)
-    k1 = play(e1, acts, "step", state_at, check_state=True)  # (check_state: no hand-over poll gave up)
-    k2 = play(e2, acts, "step", state_at, check_state=True)
+    k1 = play(e1, acts, "step", state_at, check_state=True, events=True)  # (check_state: no hand-over poll gave up)
+    k2 = play(e2, acts, "step", state_at, check_state=True, events=True)
     e1.close()
     e2.close()
     same_bytes(k1, k2)

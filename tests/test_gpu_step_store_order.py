@@ -166,7 +166,7 @@ def _play(m, gametype, base, pv, acts, f64=False):
     n = len(base)
     env = make_env(m, gametype, base, pv, f64=f64)
     big, out = _arena(torch, env, (n + 255) // 256 * 256)
-    ticks = play(env, acts, "step", every(1), out=out, check_state=True)
+    ticks = play(env, acts, "step", every(1), out=out, check_state=True, events=True)
     for b in big:  # (nothing puts the sentinel back: a tail still whole after the last tick was whole after every tick)
         tail = b[n:].contiguous().view(torch.uint8).cpu().numpy()
         assert (tail == SENTINEL).all(), ("written behind n_envs", tuple(b.shape))
@@ -236,8 +236,8 @@ def forced_split_digests(oracle_mod, tmp_path_factory):
 
 
 def _against_oracle(ticks, trace, f64=False, lanes=None):
-    """Every tick's outputs and state against the oracle's (of `lanes` of the batch, or of all of it): float32 rows as bit
-    patterns, float64 rows to sfcompare.obs_close's 1e-9."""
+    """Every tick's outputs, state and event words against the oracle's (of `lanes` of the batch, or of all of it): float32
+    rows as bit patterns, float64 rows to sfcompare.obs_close's 1e-9, the words bit for bit."""
     check_ticks(ticks, trace, "close_f64" if f64 else "f32_bits", lanes)
 
 

@@ -38,12 +38,20 @@ class StubEnv:
         self.n_actions = n_actions(gametype)
         self.calls, self.fields, self.drawn = [], {}, []
         self.rng = np.random.default_rng(77)
+        self.events = self.rollout_events = None
 
     def set_field(self, name, value):
         self.fields[name] = np.array(value)
 
+    def enable_events(self):
+        self.calls.append("enable_events")
+        self.events = torch.zeros(self.num_envs, dtype=torch.int32)
+        return self.events
+
     def _tick(self, actions, out):
         obs, rew, done, info = self.orc.step(actions.numpy().astype(np.int32))
+        if self.events is not None:  # (written in place, as the launch does: play() has to copy the row before the next tick)
+            self.events.copy_(torch.from_numpy(self.orc.events().view(np.int32)))
         res = (torch.from_numpy(obs).to(self.obs_dtype), torch.from_numpy(rew), torch.from_numpy(done.astype(np.uint8)),
                torch.from_numpy(info.astype(np.uint8)))
         if out is None:
@@ -65,7 +73,12 @@ class StubEnv:
 
     def rollout(self, actions):
         self.calls.append(("rollout", tuple(actions.shape)))
-        return tuple(torch.stack(x) for x in zip(*[self._tick(a, None) for a in actions]))
+        rows, words = [], []
+        for a in actions:
+            rows.append(self._tick(a, None))
+            words.append(None if self.events is None else self.events.clone())
+        self.rollout_events = None if self.events is None else torch.stack(words)  # (a fused launch's own [K, N] buffer)
+        return tuple(torch.stack(x) for x in zip(*rows))
 
     def state_dict(self):
         self.calls.append("state_dict")
@@ -256,6 +269,54 @@ def test_a_changed_state_shows_only_at_a_tick_state_at_selects(oracle_mod, case)
             check_ticks(got, trace, "f32_bits")
     with pytest.raises(AssertionError):  # a fused launch has no state in between to fetch
         play(StubEnv(oracle_mod, gametype, base, pv), acts, "fused", every(2))
+
+
+# ---------------------------------------------------------------- the event words
+
+@pytest.mark.parametrize("mode", ["step", "sampled", "fused"])
+def test_event_words_are_carried_by_every_mode_and_one_bit_of_one_lane_fails(oracle_mod, case, mode):
+    from spacefortress_amd._lib import EVENT_NAMES
+
+    gametype, base, pv, acts, _, plain, _ = case
+    env = StubEnv(oracle_mod, gametype, base, pv)
+    ticks = play(env, acts, mode, None, events=True)
+    assert env.calls[0] == "enable_events" and ticks.events.dtype == np.uint32 and ticks.events.shape == (T, N)
+    assert plain.events is None  # (not asked for: not there, and check_ticks does not look)
+    trace = oracle_trace(oracle_mod, gametype, base, pv, ticks.played)
+    assert all(len(tr) == 6 and tr[5].dtype == np.uint32 and tr[5].shape == (N,) for tr in trace)
+    check_ticks(ticks, trace, "f32_bits")  # an untouched copy passes
+    check_ticks(ticks._replace(events=ticks.events.copy()), trace, "f32_bits")
+    assert len({int(w) for w in ticks.events.reshape(-1)}) > 8 and not (ticks.events >> 22).any()  # (the run has events to get wrong)
+    # one bit of one lane of one tick: set where it is clear, cleared where it is set, flipped -- every one of the 22 bits,
+    # at a tick and a lane that move with the bit
+    for k, bit in enumerate(sorted(EVENT_NAMES)):
+        t, lane = k % T, (7 * k + 3) % N
+        w = int(ticks.events[t, lane])
+        for change in (lambda v: v | np.uint32(bit), lambda v: v & ~np.uint32(bit), lambda v: v ^ np.uint32(bit)):
+            if int(change(np.uint32(w))) == w:
+                check_ticks(_changed(ticks, "events", (t, lane), change), trace, "f32_bits")
+                continue
+            with pytest.raises(AssertionError) as e:
+                check_ticks(_changed(ticks, "events", (t, lane), change), trace, "f32_bits")
+            where = e.value.args[0]
+            assert where[:3] == (t, "events", [lane]), where
+            got, want = where[3][0]  # the names on both sides: they differ by the changed bit's name
+            assert set(got) ^ set(want) == {EVENT_NAMES[bit]}, where
+    # a bit the oracle has and the batch has not, found by name: the first set bit of the run
+    t, lane = [int(x) for x in np.argwhere(ticks.events != 0)[0]]
+    _fails(_changed(ticks, "events", (t, lane), lambda v: v & (v - np.uint32(1))), trace, "f32_bits", (t, "events"))
+    # a trace without words cannot vouch for a batch that has them
+    with pytest.raises(AssertionError):
+        check_ticks(ticks, [tr[:5] for tr in trace], "f32_bits")
+    # lanes outside a selection are not looked at
+    lanes = np.array([3, 4, 20, 41, 63])
+    sub = oracle_trace(oracle_mod, gametype, base, pv, ticks.played, lanes)
+    check_ticks(_changed(ticks, "events", (2, 5), lambda v: v ^ np.uint32(1)), sub, "f32_bits", lanes)
+    _fails(_changed(ticks, "events", (2, 41), lambda v: v ^ np.uint32(1)), sub, "f32_bits", (2, "events"), lanes)
+    # and same_bytes reads them where both sides have them
+    same_bytes(ticks, ticks)
+    with pytest.raises(AssertionError):
+        same_bytes(ticks, _changed(ticks, "events", (T - 1, N - 1), lambda v: v ^ np.uint32(0x200000)))
 
 
 # ---------------------------------------------------------------- selection
