@@ -15,11 +15,13 @@ once, the actor reads the current stack that step() returns and the minibatches 
 
     python examples/ppo_loop.py --obs image --envs 1024 --steps 32 --iters 5
 
---time-limit-bootstrap (features): every episode of this game ends by the clock, so `done` is a truncation; the rollout keeps
-each env's final observation and the returns bootstrap with the critic's value of it instead of 0 -- one more critic forward
-per update (DeviceRollout(time_limit_bootstrap=True), INTEGRATION.md "Episodes end by the clock").
+--time-limit-bootstrap: every episode of this game ends by the clock, so `done` is a truncation; the rollout keeps each env's
+final observation (image: its final stack of frames, include/sfmi_final.h) and the returns bootstrap with the critic's value of
+it instead of 0 -- one more critic forward per update (DeviceRollout / FrameRollout(time_limit_bootstrap=True), INTEGRATION.md
+"Episodes end by the clock").  Not with --frame-skip > 1 on images.
 
     python examples/ppo_loop.py --time-limit-bootstrap --envs 256 --steps 16 --iters 2
+    python examples/ppo_loop.py --obs image --time-limit-bootstrap --envs 256 --steps 16 --iters 2
 
 --frame-skip K: every action is played for K ticks by one launch (SFVecEnv(frame_skip=K), include/sfmi_repeat.h); rewards are
 summed over the window, an env that finishes inside it stops there, an image batch draws one frame per action.  Default 1.
@@ -77,7 +79,7 @@ class ConvActorCritic(nn.Module):
 def main_image(a):
     """The image path: FrameRollout instead of DeviceRollout(env, T, num_stack=4); no `observations` tensor anywhere."""
     env = SFVecEnv(a.envs, gametype=a.gametype, obs_type="image", spawn_stride=1, frame_skip=a.frame_skip)
-    ro = FrameRollout(env, a.steps, num_stack=4)
+    ro = FrameRollout(env, a.steps, num_stack=4, time_limit_bootstrap=a.time_limit_bootstrap)
     net = ConvActorCritic(4, env.n_actions).to(env.device)
     opt = torch.optim.Adam(net.parameters(), lr=7e-4)
     cur = ro.reset()
@@ -92,7 +94,9 @@ def main_image(a):
             cur, _, _ = ro.step(t, action, value_pred=value, action_log_prob=dist.log_prob(action).unsqueeze(1))
         with torch.no_grad():
             next_value = net(cur.float())[1]
-        ro.compute_returns(next_value, True, 0.99, 0.95)
+            # the critic's value of every env's final stack: used where masks == 0 only
+            final_value = net(ro.final_obs().float())[1] if a.time_limit_bootstrap else None
+        ro.compute_returns(next_value, True, 0.99, 0.95, final_value=final_value)
         adv = ro.returns[:-1] - ro.value_preds[:-1]
         adv = (adv - adv.mean()) / (adv.std() + 1e-5)
         for _ in range(a.ppo_epochs):
@@ -125,14 +129,14 @@ def main():
     ap.add_argument("--ppo-epochs", type=int, default=4)
     ap.add_argument("--mini-batches", type=int, default=4)
     ap.add_argument("--time-limit-bootstrap", action="store_true",
-                    help="features: bootstrap the returns at an episode's end with V(final observation) instead of 0")
+                    help="bootstrap the returns at an episode's end with V(final observation / final frame stack) instead of 0")
     ap.add_argument("--frame-skip", type=int, default=1, metavar="K",
                     help="ticks every action is played for, in one launch (1: a tick per step)")
     a = ap.parse_args()
     torch.manual_seed(0)
     if a.obs == "image":
-        if a.time_limit_bootstrap:
-            ap.error("--time-limit-bootstrap is for --obs features (image batches have no final-observation output)")
+        if a.time_limit_bootstrap and a.frame_skip > 1:
+            ap.error("--time-limit-bootstrap with --obs image needs --frame-skip 1 (the action repeat has no final frames yet)")
         return main_image(a)
     envs = SFVecNormalize(SFVecEnv(a.envs, gametype=a.gametype, spawn_stride=1, frame_skip=a.frame_skip))
     log = envs.venv.enable_episode_log()

@@ -189,6 +189,12 @@ HOLD_SYMBOLS = {
     "sf_step_where": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
 }
 
+# every symbol include/sfmi_final.h declares (final frames of image batches): bound like SYMBOLS
+FINAL_SYMBOLS = {
+    "sf_set_final_frame_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "sf_final_stack_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+}
+
 # what the wrappers answer to `.reset_lanes`: their per-env memory would go stale behind a masked reset
 NO_RESET_LANES = ("%s has no reset_lanes(): its per-env memory (frame stacks, return accumulators, start flags, masks) has no "
                   "rule for a masked reset yet.  Call SFVecEnv.reset_lanes on the bare env and rebuild the wrapper's state, or "
@@ -207,7 +213,7 @@ def lib():
                 "(there is no CPU fallback)" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(MASKED_SYMBOLS.items()) + list(REPEAT_SYMBOLS.items()) \
-                + list(HOLD_SYMBOLS.items()):
+                + list(HOLD_SYMBOLS.items()) + list(FINAL_SYMBOLS.items()):
             if not hasattr(L, name) and os.environ.get("SFMI_LIB_PATH"):
                 continue  # an older diagnostic build (A/B against an earlier round's library): entry points added since
             f = getattr(L, name)

@@ -139,6 +139,13 @@ struct sf_batch {
   // sf_step_where (sfmi_hold.h): where the held envs wait while the others tick -- a buffer of the state's size, tile
   // layout, made by the first masked step
   DevBuf<unsigned char> d_hold;
+  // sf_set_final_frame_output (sfmi_final.h): the caller's buffer (null: off) and its env stride in bytes; the done bytes of a
+  // step the caller gave no done_dev; the default geometry's hexagons and INTER_AREA taps in the general renderer's table
+  // forms (the painter draws the final frames in every geometry).  Made by the first setter call that switches the output on
+  uint8_t* final_frames = nullptr;
+  size_t final_stride = 0;
+  DevBuf<uint8_t> d_fdone, d_fbg;
+  DevBuf<uint32_t> d_ftabs;
 };
 
 inline bool sfb_is_image(const sf_batch* b) { return b->obs_mode == SF_OBS_IMAGE || b->obs_mode == SF_OBS_IMAGE_RAW; }
@@ -150,6 +157,11 @@ int sfb_flush_missile_view(sf_batch* b, hipStream_t stream);
 
 // sf_image_capi.cpp: the image observation's tables of a new batch (sf_create); what a batch needs to draw frames, made once;
 // the envs' draw records from the state as it is; one frame per env, or one slot of a frame stack
+// sf_final_capi.cpp: behind a step launch that ran with auto_reset off and wrote `done` -- the finished envs' frames into the
+// final-frame output, then their episode totals, new games and draw records (sf_launch_finish_lanes); and, in front of that
+// step launch, whether the output's buffer still fits the batch's geometry, which may have changed since the setter
+int sfb_finish_with_final_frames(sf_batch* b, const uint8_t* done, hipStream_t stream);
+int sfb_final_frames_fit(const sf_batch* b, const char* who);
 int sfb_create_image_tables(sf_batch* b);
 int sfb_ensure_render_resources(sf_batch* b, hipStream_t stream);
 int sfb_rebuild_draw_records(sf_batch* b, hipStream_t stream);

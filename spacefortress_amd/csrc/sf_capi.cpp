@@ -327,6 +327,13 @@ static int launch_steps(sf_batch* b, const StepLaunch& d, void* obs_dev, void* s
     args.n_gamma = d.n_gamma;
   }
   const void* actions = sampled ? b->d_actrec.get() : d.actions;
+  // final frames (sfmi_final.h): the step launches run with auto-reset off, tick by tick, and every one is followed by the
+  // finished envs' frames and their finish -- totals, new games, draw records (sfb_finish_with_final_frames)
+  const bool finals = b->final_frames != nullptr;
+  if (finals) {
+    SF_TRY(sfb_final_frames_fit(b, d.who));
+    args.auto_reset = 0;
+  }
   SF_FLUSH_VIEW(b, stream);
   // a masked step: the held envs leave in front of the launch and come back behind it, with their output rows -- and, image
   // batches, their draw records -- in front of the frames
@@ -344,7 +351,7 @@ static int launch_steps(sf_batch* b, const StepLaunch& d, void* obs_dev, void* s
     if (image && obs_dev) return sfb_render(b, b->obs_mode, (uint8_t*)obs_dev, 0, (hipStream_t)stream);
     return SF_OK;
   }
-  if (!(image && obs_dev)) {
+  if (!(image && obs_dev) && !finals) {
     STEP_TRY(sf_launch_step(args, b->autoturn, b->preset.shaped != 0, actions, d.act_type, image ? nullptr : obs_dev, d.reward,
                            d.done, d.info, d.n_steps, d.fused, (hipStream_t)stream));
     HIP_TRY(held_back());
@@ -354,18 +361,22 @@ static int launch_steps(sf_batch* b, const StepLaunch& d, void* obs_dev, void* s
   // frames are rendered from the state in HBM, which the fused launch keeps in registers: with frames asked for, the K ticks
   // go out as K step launches, each followed by its frames -- what K sf_step calls do, in one call.  (Sampled actions: the
   // tiles' tick counters move on by one per launch, so the actions drawn are the fused launch's.)
+  // (final frames: the same K launches with or without frames asked for -- the finish needs the state in HBM between ticks)
   const size_t n = (size_t)b->n_envs, frame = (size_t)sf_obs_dim(b);
   for (int t = 0; t < d.n_steps; t++) {
     const size_t row = (size_t)t * n;  // (a rollout's outputs, event masks included, are [n_steps][n_envs])
     SfKernelArgs at = args;
     if (at.act_out) at.act_out += row;
     if (at.events) at.events += row;
+    uint8_t* const done_t = d.done ? d.done + row : (finals ? b->d_fdone.get() : nullptr);  // (the finish reads the tick's done bytes)
     STEP_TRY(sf_launch_step(at, b->autoturn, b->preset.shaped != 0,
                            sampled ? actions : (const unsigned char*)actions + row * (size_t)d.act_type, d.act_type, nullptr,
-                           d.reward ? d.reward + row : nullptr, d.done ? d.done + row : nullptr, d.info ? d.info + row : nullptr,
+                           d.reward ? d.reward + row : nullptr, done_t, d.info ? d.info + row : nullptr,
                            1, false, (hipStream_t)stream));
     HIP_TRY(held_back());  // (a masked step is one tick: n_steps == 1)
+    if (finals) SF_TRY(sfb_finish_with_final_frames(b, done_t, (hipStream_t)stream));
     b->draw_current = b->args.draw != nullptr;
+    if (!obs_dev) continue;
     const int rc = sfb_render(b, b->obs_mode, (uint8_t*)obs_dev + row * frame, 0, (hipStream_t)stream);
     if (rc != SF_OK) return rc;
   }
@@ -401,6 +412,12 @@ extern "C" int sf_step_repeat(sf_batch* b, const void* actions_dev, int act_type
                  "would have to be frozen in place, and a parked lane is given its new game; step such a batch tick by tick");
     return SF_ERR_ARG;
   }
+  if (repeat > 1 && b->final_frames) {
+    sf_set_error("sf_step_repeat: no action repeat while a final-frame output is set (sf_set_final_frame_output): an env parked "
+                 "inside the window no longer holds its last frame's state; final frames of a repeat window are a follow-up -- "
+                 "switch the output off (NULL) or step with repeat 1");
+    return SF_ERR_ARG;
+  }
   StepLaunch d{"sf_step_repeat", actions_dev, act_type, 1, false, reward_dev, done_dev, info_dev, repeat, ticks_dev};
   const int rc = launch_steps(b, d, obs_dev, stream);
   if (rc != SF_OK || repeat > 1) return rc;
@@ -425,6 +442,12 @@ extern "C" int sf_step_where(sf_batch* b, const uint8_t* active_dev, const void*
   if (repeat > 1 && !b->args.auto_reset) {
     sf_set_error("sf_step_where: a SF_FLAG_NO_AUTO_RESET batch has no action repeat (sf_step_repeat: an ACTIVE env that finishes "
                  "inside the window would be given its new game); step such a batch with repeat 1");
+    return SF_ERR_ARG;
+  }
+  if (b->final_frames) {
+    sf_set_error("sf_step_where: no masked step while a final-frame output is set (sf_set_final_frame_output): the held envs' "
+                 "stand-ins would finish and restart in their place; final frames of a masked step are a follow-up -- switch "
+                 "the output off (NULL) first");
     return SF_ERR_ARG;
   }
   if (!b->d_hold) {  // the first masked step of this batch (not capturable: it allocates)
@@ -566,8 +589,9 @@ extern "C" int sf_set_final_obs_output(sf_batch* b, void* final_obs_dev) {
   if (!b) return SF_ERR_ARG;
   if (final_obs_dev != nullptr) {  // (switching it off is always possible)
     if (sfb_is_image(b)) {
-      sf_set_error("sf_set_final_obs_output: image batches have no final-observation output; create the batch with "
-                   "SF_FLAG_NO_AUTO_RESET, read the finished envs' frames and restart them with sf_reset_lanes");
+      sf_set_error("sf_set_final_obs_output: image batches have no final-observation rows; their finished games' last frames "
+                   "come from sf_set_final_frame_output (sfmi_final.h) -- or create the batch with SF_FLAG_NO_AUTO_RESET, read "
+                   "the finished envs' frames and restart them with sf_reset_lanes");
       return SF_ERR_ARG;
     }
     if (!b->args.auto_reset) {

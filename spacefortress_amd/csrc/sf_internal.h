@@ -6,6 +6,7 @@
 #include "sf_glyphs.h"
 #include "sf_layout.h"
 #include "sfmi.h"
+#include "sfmi_final.h"
 #include "sfmi_hold.h"
 #include "sfmi_masked.h"
 #include "sfmi_repeat.h"
@@ -31,6 +32,21 @@ hipError_t sf_launch_drawrec(const SfKernelArgs& a, hipStream_t stream);
 hipError_t sf_launch_hold_begin(const SfKernelArgs& a, const uint8_t* active, unsigned char* stash, hipStream_t stream);
 hipError_t sf_launch_hold_end(const SfKernelArgs& a, const uint8_t* active, const unsigned char* stash, void* obs, int32_t* reward,
                               uint8_t* done, uint8_t* info, uint8_t* ticks, int one_tick, hipStream_t stream);
+
+// final frames (sfmi_final.h), behind a step launch that ran with auto_reset off: the envs whose byte of done [n_envs] is not
+// zero finish as the in-kernel auto-reset finishes them -- episode totals into a.acc, a new game on the lane's own prev_vlner
+// and spawn cursor, their missiles out of the tile's pool, their hint bits cleared -- and, where a.draw is set, their draw
+// records follow the new state (the others' are the step launch's own and stay)
+hipError_t sf_launch_finish_lanes(const SfKernelArgs& a, const uint8_t* done, hipStream_t stream);
+
+// sf_final_frames.hip: sf_launch_render_generic (below) for the envs whose byte of done [n_envs] is not zero -- one workgroup
+// per env, which returns at once on a zero byte; no row of `out` but a finished env's is written
+hipError_t sf_launch_final_frames(const unsigned char* state, const uint8_t* done, int n_envs, int W, int H, double sx, double sy,
+                                  double vp_x, double vp_y, double line_w, const double* trig, const double* arcs, const uint8_t* bg,
+                                  const uint32_t* tabs, uint8_t* out, size_t out_stride, int resize, const SfGlyphAtlas* glyphs,
+                                  hipStream_t stream);
+hipError_t sf_launch_final_stack_shift(const uint8_t* prev, uint8_t* fin, int num_stack, size_t frame_bytes, const uint8_t* done,
+                                       int n_envs, hipStream_t stream);
 
 // gather (to_linear) / scatter one field between the tiled state and a linear [count][n_envs] buffer
 hipError_t sf_launch_field_copy(unsigned char* state, int n_envs, int field, unsigned char* linear, int to_linear,

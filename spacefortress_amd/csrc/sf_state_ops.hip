@@ -59,9 +59,12 @@ __device__ __forceinline__ unsigned pool_rebuild(unsigned char* tb, unsigned mas
 // pool may differ, which no row and no tick can tell); the lanes behind the batch in a partial last tile count as kept.
 // obs (may be null): the marked lanes' rows as sf_reset_kernel writes them; no other row is touched.  hint (image batches):
 // the marked lanes' bits are cleared -- a new game's ship did not die in the last tick.
-__global__ __launch_bounds__(64) void sf_reset_lanes_kernel(SfKernelArgs a, const uint8_t* mask, void* obs) {
-  __shared__ d2_t spos[64][SF_NSLOT];
-  __shared__ unsigned short sang[64][SF_NSLOT];
+// FINISH (sf_finish_lanes_kernel, sfmi_final.h): the marked lanes are games that ENDED in the step launch in front, which ran
+// with auto_reset off -- before the new game their episode totals go into a.acc, from the lane's counters as that launch left
+// them, exactly as the step kernel's own auto-reset adds them (sf_kernels.hip: "episode totals")
+template <bool FINISH>
+__device__ __forceinline__ void reset_lanes_tile(const SfKernelArgs& a, const uint8_t* mask, void* obs, d2_t (*spos)[SF_NSLOT],
+                                                 unsigned short (*sang)[SF_NSLOT]) {
   const unsigned lane = threadIdx.x;
   const long tile_i = blockIdx.x;
   const long e = tile_i * 64 + lane;
@@ -73,6 +76,24 @@ __global__ __launch_bounds__(64) void sf_reset_lanes_kernel(SfKernelArgs a, cons
   // everything that is read from the tile, first
   const i4_t mi = SF_LD(i4_t, SF_CHUNK(misc, 0), o.o16);
   const unsigned pvl_w = SF_LD(unsigned, SF_CHUNK(timers_a, 0), o.o16);
+  if constexpr (FINISH) {
+    if (marked) {
+      Lane F;
+      load_lane_early(tb, o, F);
+      unpack_lane_late(load_lane_late(tb, o), F);
+      const int ep_ret = F.ep_return, ep_kil = (int)F.ep_kills;
+      const int deaths = (int)(F.c_big + F.c_small + F.c_shell);
+      const int shots = (int)(F.kc0 & 0xFFFFu);
+      atomicAdd(&a.acc[0], 1ull);
+      atomicAdd(&a.acc[1], (unsigned long long)(long long)ep_ret);
+      atomicAdd(&a.acc[2], (unsigned long long)((long long)ep_ret * ep_ret));
+      atomicAdd(&a.acc[3], (unsigned long long)(long long)ep_kil);
+      atomicAdd(&a.acc[4], (unsigned long long)deaths);
+      atomicAdd(&a.acc[5], (unsigned long long)shots);
+      atomicMin((long long*)&a.acc[6], (long long)ep_ret);
+      atomicMax((long long*)&a.acc[7], (long long)ep_ret);
+    }
+  }
   pool_for_each(tb, (unsigned)__builtin_amdgcn_readfirstlane(mi.z), lane, [&](unsigned i, unsigned m) {  // (the same word's count in every lane)
     const unsigned ow = SF_MM_OWNER(m);
     if (!((rmask >> ow) & 1ull)) {
@@ -95,6 +116,18 @@ __global__ __launch_bounds__(64) void sf_reset_lanes_kernel(SfKernelArgs a, cons
     if (obs != nullptr && a.obs_type != 3) write_obs_row(a, obs, (size_t)e, L, new_game_extras(a, L));  // (as sf_reset_kernel)
   }
   if (a.hint && lane == 0) a.hint[tile_i] &= ~rmask;
+}
+
+__global__ __launch_bounds__(64) void sf_reset_lanes_kernel(SfKernelArgs a, const uint8_t* mask, void* obs) {
+  __shared__ d2_t spos[64][SF_NSLOT];
+  __shared__ unsigned short sang[64][SF_NSLOT];
+  reset_lanes_tile<false>(a, mask, obs, spos, sang);
+}
+
+__global__ __launch_bounds__(64) void sf_finish_lanes_kernel(SfKernelArgs a, const uint8_t* done) {
+  __shared__ d2_t spos[64][SF_NSLOT];
+  __shared__ unsigned short sang[64][SF_NSLOT];
+  reset_lanes_tile<true>(a, done, nullptr, spos, sang);
 }
 
 hipError_t sf_launch_reset_lanes(const SfKernelArgs& a, const uint8_t* mask, void* obs, hipStream_t stream) {
@@ -753,6 +786,24 @@ __global__ __launch_bounds__(64) void sf_hold_drawrec_kernel(const unsigned char
   const unsigned long long hmask = __ballot(e < n_envs && active[e] == 0);
   if (hmask == 0ull) return;  // (uniform)
   drawrec_tile(state, n_envs, draw, pics, hmask, near);
+}
+
+// The finished lanes' draw records from their new games, behind sf_finish_lanes_kernel: sf_drawrec_kernel's code for the lanes of
+// the done bytes' non-zeros; the others' records are the step launch's own and stay.
+__global__ __launch_bounds__(64) void sf_finish_drawrec_kernel(const unsigned char* state, int n_envs, const uint8_t* done, unsigned char* draw,
+                                                              int pics) {
+  __shared__ unsigned near[64];
+  const long e = (long)blockIdx.x * 64 + threadIdx.x;
+  const unsigned long long fmask = __ballot(e < n_envs && done[e] != 0);
+  if (fmask == 0ull) return;  // (uniform)
+  drawrec_tile(state, n_envs, draw, pics, fmask, near);
+}
+
+hipError_t sf_launch_finish_lanes(const SfKernelArgs& a, const uint8_t* done, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.n_envs + 63) / 64));
+  hipLaunchKernelGGL(sf_finish_lanes_kernel, grid, dim3(64), 0, stream, a, done);
+  if (a.draw) hipLaunchKernelGGL(sf_finish_drawrec_kernel, grid, dim3(64), 0, stream, a.state, a.n_envs, done, a.draw, a.draw_pics);
+  return hipGetLastError();
 }
 
 hipError_t sf_launch_hold_begin(const SfKernelArgs& a, const uint8_t* active, unsigned char* stash, hipStream_t stream) {

@@ -53,10 +53,6 @@ def gather_errors(device, clear=False):
 
 class FrameRollout(DeviceRollout):
     def __init__(self, env, num_steps, state_size=1, num_stack=4, layout="time", time_limit_bootstrap=False):
-        if time_limit_bootstrap:
-            raise ValueError("FrameRollout: time_limit_bootstrap is for 1-D observations: image batches have no "
-                             "final-observation output; make the env with auto_reset=False, read the finished envs' frames "
-                             "and restart them with reset_lanes(mask=done)")
         if hasattr(env, "venv"):
             raise ValueError("FrameRollout stores image observations: no SFVecNormalize around the env (rl/train.py:35)")
         if env.obs_type != "image" or not env.default_geometry:
@@ -67,7 +63,8 @@ class FrameRollout(DeviceRollout):
             raise ValueError("layout is 'time' ([rows][n][7056]) or 'env' ([n][rows][7056])")
         self.layout = layout
         self._S = int(num_stack)
-        super().__init__(env, num_steps, state_size=state_size, num_stack=num_stack)
+        # (time_limit_bootstrap: DeviceRollout's final stack [n, S, 84, 84]; the stack a step starts from is self._cur)
+        super().__init__(env, num_steps, state_size=state_size, num_stack=num_stack, time_limit_bootstrap=time_limit_bootstrap)
 
     def _alloc_observations(self, shape):
         T, n, S, dev = self.num_steps, self.env.num_envs, self._S, self.env.device
@@ -155,6 +152,7 @@ class FrameRollout(DeviceRollout):
             "act": [vp(self.actions[t].data_ptr()) for t in range(T)],
             "r": vp(self._rew.data_ptr()), "i": vp(self._info.data_ptr()),
             "ep": vp(self.episode_rewards.data_ptr()), "fin": vp(self.final_rewards.data_ptr()),
+            "cur": vp(self._cur.data_ptr()),
         }
         self._start_rows = [self.starts[H + t] for t in range(T + 1)]
         # what step() returns: the current stack lives in ONE reused buffer (the next step overwrites it)
@@ -164,6 +162,7 @@ class FrameRollout(DeviceRollout):
         e, P = self.env, self._ptr
         # the step's done bytes are the start flags of frame step + 1: the kernel writes them straight into their row
         self._step_and_record(a, ap, at, step, None, self._start_rows[step + 1], P["start"][step + 1], stream)
+        self._shift_final_stack(P["cur"], P["start"][step + 1], stream)  # (before the gather below overwrites the stack)
         _lib.check(self._L.sf_render(e._h, _lib.OBS_TYPES["image"], P["row"][step + 1], self._env_stride, stream))
         self._gather(None, e.num_envs, step + 1, self._cur)
 

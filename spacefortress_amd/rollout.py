@@ -16,6 +16,10 @@ observation (SFVecEnv.enable_final_obs), `final_obs()` hands the rows to the cri
 game ended on (`sf_compute_returns_tl`).  One row per env describes one finish: num_steps <= env.max_ticks + 1, the length
 of an episode.  A caller who shortens episodes behind the rollout's back -- set_field("time"), load_lanes -- so that an env
 finishes twice inside one rollout gets the LATER observation's value for both.
+
+Image envs (num_stack >= 1) bootstrap the same way with the finished game's last STACK: the rollout owns a [N, S, 84, 84] final
+stack, points the env's final-frame output (SFVecEnv.enable_final_frames, sfmi_final.h) at its last slot, and after every step
+copies the finished envs' history -- slots 1 .. S-1 of the stack the step started from -- in front of it (sf_final_stack_shift).
 """
 import ctypes as C
 
@@ -36,15 +40,16 @@ class DeviceRollout:
         T, n, dev = int(num_steps), env.num_envs, env.device
         self.num_steps = T
         self.time_limit_bootstrap = bool(time_limit_bootstrap)
+        self._final_stack = None
         if self.time_limit_bootstrap:
-            if int(num_stack) > 1 or env.is_image:
-                raise ValueError("time_limit_bootstrap is for 1-D observations: a stack of frames has no final-observation "
-                                 "output; make the env with auto_reset=False, read the finished envs' frames and restart "
-                                 "them with reset_lanes(mask=done)")
+            if int(num_stack) > 1 and not env.is_image:
+                raise ValueError("time_limit_bootstrap with num_stack > 1 is for obs_type='image': 1-D observations are not stacked")
+            if env.is_image and self.norm is not None:
+                raise ValueError("time_limit_bootstrap on image observations: no SFVecNormalize around the env (rl/train.py:35)")
             if T > env.max_ticks + 1:
                 raise ValueError("time_limit_bootstrap: num_steps %d > %d, the ticks of an episode: an env would finish twice "
                                  "in a rollout and one final observation per env cannot describe both" % (T, env.max_ticks + 1))
-            if env.final_obs is None:
+            if not env.is_image and env.final_obs is None:
                 env.enable_final_obs()
         obs_shape = tuple(env.obs_shape)
         # image observations: obs_shape = (obs_shape[0] * num_stack, ...) as in rl/train.py:38-39; every step stores
@@ -54,6 +59,12 @@ class DeviceRollout:
             if env.obs_type != "image" or self.norm is not None:
                 raise ValueError("num_stack > 1 is for obs_type='image' (rl/train.py:38-39)")
             obs_shape = (self.num_stack,) + obs_shape[1:]
+        if self.time_limit_bootstrap and env.is_image:
+            # the final stack: the env writes a finished game's last frame straight into its last slot (refuses auto_reset=False,
+            # frame_skip > 1), sf_final_stack_shift fills the slots in front of it
+            self._final_stack = torch.zeros((n,) + obs_shape, dtype=torch.uint8, device=dev)
+            last = self._final_stack[:, self.num_stack - 1:] if env.obs_type == "image" else self._final_stack
+            env.enable_final_frames(out=last)
         self._alloc_observations((T + 1, n) + obs_shape)
         self.states = torch.zeros(T + 1, n, state_size, device=dev)
         self.rewards = torch.zeros(T, n, 1, device=dev)
@@ -179,10 +190,18 @@ class DeviceRollout:
             self.observations[step + 1][:, :-1].copy_(self.observations[step][:, 1:])
             _lib.check(self._L.sf_render_stack(e._h, P["obs"][step + 1], self.num_stack, self.num_stack - 1, P["d"], stream))
 
+    def _shift_final_stack(self, prev, done, stream):
+        """The finished envs' history into the final stack: slots 1 .. S-1 of `prev` (the address of the stack the step started
+        from) in front of the final frame the step wrote into the last slot (sfmi_final.h: sf_final_stack_shift)."""
+        fs = self._final_stack
+        if fs is not None and self.num_stack > 1:
+            _lib.check(self._L.sf_final_stack_shift(prev, ptr(fs), self.num_stack, fs[0, 0].numel(), done, self.env.num_envs, stream))
+
     def _step_record(self, a, ap, at, step, stream):
         P = self._ptr
         if self.num_stack > 1:  # the step without an observation, then the stack
             self._step_and_record(a, ap, at, step, None, self._done, P["d"], stream)
+            self._shift_final_stack(P["obs"][step], P["d"], stream)
             self._advance_stack(step, stream)
         else:
             self._step_and_record(a, ap, at, step, P["obs"][step + 1], self._done, P["d"], stream)
@@ -194,10 +213,12 @@ class DeviceRollout:
 
     def final_obs(self):
         """[N, obs_dim]: every env's final observation as the agent sees observations -- through the normaliser when there is
-        one (a copy, statistics as they stand: SFVecNormalize.final_obs), else the env's own rows.  For the critic:
-        compute_returns(..., final_value=critic(ro.final_obs()))."""
+        one (a copy, statistics as they stand: SFVecNormalize.final_obs), else the env's own rows; image envs: the rollout's
+        final stack [N, S, 84, 84].  For the critic: compute_returns(..., final_value=critic(ro.final_obs()))."""
         if not self.time_limit_bootstrap:
             raise ValueError("final_obs(): this rollout was made without time_limit_bootstrap=True")
+        if self._final_stack is not None:
+            return self._final_stack
         return self.norm.final_obs() if self.norm is not None else self.env.final_obs
 
     def compute_returns(self, next_value, use_gae, gamma, tau, final_value=None):

@@ -53,6 +53,7 @@ class SFVecEnv:
                              "frozen in place for the rest of the window (sfmi_repeat.h)")
         self.last_ticks = None  # uint8 [N]: the ticks every env played in the last step_repeat call
         self._own_ticks = None
+        self._final_frames = None
         if self.frame_skip > 1:
             self.step_tensors = self._step_tensors_skip
         self._L = _lib.lib()
@@ -265,6 +266,9 @@ class SFVecEnv:
         if not (torch.is_tensor(active) and active.dtype in (torch.uint8, torch.bool) and active.device == self.device
                 and active.dim() == 1 and active.numel() == n and active.is_contiguous()):
             raise ValueError("step_where: active must be a contiguous uint8 or bool tensor [%d] on %s" % (n, self.device))
+        if self._final_frames is not None:
+            raise ValueError("step_where() while final frames are enabled (enable_final_frames): the masked step has no "
+                             "final-frame output yet; enable_final_frames(False) first")
         if self._rec is not None:
             raise ValueError("step_where() during a recording: a replay file holds one action per env and step, and a held "
                              "env plays none")
@@ -319,6 +323,9 @@ class SFVecEnv:
         else:
             if repeat is None:
                 repeat = self.frame_skip
+            if repeat > 1 and self._final_frames is not None:
+                raise ValueError("step_repeat() while final frames are enabled (enable_final_frames): an action repeat has no "
+                                 "final-frame output yet; enable_final_frames(False) first, or step with repeat 1")
             if repeat != 1:
                 self._no_duration_log("step_repeat()")
             if self._rec is not None and repeat > 1:
@@ -518,6 +525,7 @@ class SFVecEnv:
             self._L.sf_destroy(self._h)
             self._h = None
         self._final_obs = None
+        self._final_frames = None
 
     def __del__(self):
         try:
@@ -662,8 +670,8 @@ class SFVecEnv:
             self._final_obs = None
             return None
         if self.is_image or self.obs_type == "none":
-            raise ValueError("enable_final_obs: image batches have no final-observation output; make the batch with "
-                             "auto_reset=False, read the finished envs' frames and restart them with reset_lanes(mask=done)")
+            raise ValueError("enable_final_obs: image batches have no final-observation rows; their finished games' last "
+                             "frames come from enable_final_frames()")
         if out is None:
             out = torch.zeros((self.num_envs, self.obs_dim), dtype=self.obs_dtype, device=self.device)
         elif not (torch.is_tensor(out) and out.device == self.device and out.dtype == self.obs_dtype and out.is_contiguous()
@@ -678,6 +686,43 @@ class SFVecEnv:
     def final_obs(self):
         """The tensor enable_final_obs() handed to the library, or None."""
         return getattr(self, "_final_obs", None)
+
+    def enable_final_frames(self, out=None):
+        """The LAST frame of every game that ends, for image batches (sfmi_final.h: sf_set_final_frame_output): from here on
+        step / step_tensors / step_sampled / rollout / rollout_sampled and DeviceRollout's sf_step_record write, for each env
+        whose `done` they set, the frame of the finished game after its last tick -- the one the auto-reset replaces with the
+        new game's first frame -- into a uint8 tensor [N, 1, 84, 84] ('image') or [N, h, w] ('image-raw', the batch's
+        geometry), and leave the other rows alone.  Everything else the step does stays byte for byte what it was.  Allocates
+        a zeroed tensor or adopts `out` (frames contiguous; the env stride may be larger: the last slot of a [N, S, 84, 84]
+        stack), returns it (also `self.final_frames`); enable_final_frames(False) switches it off.  Off by default: with it on
+        a step is the general step launch and three more launches that leave at once unless an env finishes (+16.5 us per step
+        at 16 384 envs, +5 us at 256: profiles/final_frames.md).  ValueError for batches without image observations, auto_reset=False, frame_skip > 1 and
+        a misaligned buffer; while it is on, step_repeat (repeat > 1) and step_where raise ValueError."""
+        if out is False:
+            _lib.check(self._L.sf_set_final_frame_output(self._h, None, 0))
+            self._final_frames = None
+            return None
+        if not self.is_image:
+            raise ValueError("enable_final_frames: this batch has no image observations; the finished games' last observation "
+                             "rows come from enable_final_obs()")
+        if self.frame_skip > 1:
+            raise ValueError("enable_final_frames: a batch with frame_skip > 1 steps through the action repeat, which has no "
+                             "final-frame output yet")
+        shape = (self.num_envs,) + tuple(self.obs_shape)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+        elif not (torch.is_tensor(out) and out.device == self.device and out.dtype == torch.uint8 and tuple(out.shape) == shape
+                  and out[0].is_contiguous()):
+            raise ValueError("enable_final_frames: out must be a uint8 tensor %s on %s with contiguous frames" % (shape, self.device))
+        stride = out.stride(0) if self.num_envs > 1 else 0
+        _lib.check(self._L.sf_set_final_frame_output(self._h, C.c_void_p(out.data_ptr()), stride))  # (refuses auto_reset=False, misalignment)
+        self._final_frames = out
+        return out
+
+    @property
+    def final_frames(self):
+        """The tensor enable_final_frames() handed to the library, or None."""
+        return self._final_frames
 
     # ------------------------------------------------------------------ extras
     def check_actions(self):
