@@ -648,7 +648,7 @@ static void tor_render(ctx_t* c, int grey) {
         cover += ce->covered_height * GRID_X * 2;
         int area = cover - ce->uncovered_area;
         unsigned a = (unsigned)AREA_TO_ALPHA(area);
-        if (a > 255) a = 255;
+        a &= 255u; /* the span's coverage is a uint8_t (cairo_half_open_span_t): 256 wraps to 0 */
         for (int yy = i; yy < j; yy++) put_cov(c, x, yy + ymin, a, grey);
       }
     }

@@ -333,6 +333,10 @@ Box4 user_rect(const Geometry& g, double x, double y, double w, double h) {
 
 // ================= 2. the kernels' formulation, on the host =====================================================================
 // accumulate the object's coverage (0..7680 per pixel) into acc[H][W]
+// KNOWN DIFFERENCE from the kernels (sf_tor_dev.h: raster): a row's mode here looks at the quads' vertices only; the kernels also
+// count the path's point at a circle's curve seam (cairo's inner_join), which matters for a circle whose stroke is wide against
+// its radius (line width 4.5 at .75 pixels per unit and above).  The callers of this function draw two-curve circles at line
+// widths up to 3, where no row is decided differently; profiles/view_edge_tests.md, finding 3.
 void object_coverage(const Object& ob, int W, int H, int* acc) {
   const int nq = ob.nq;
   std::vector<sft::QuadScan> qs(nq);

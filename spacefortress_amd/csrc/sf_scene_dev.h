@@ -241,10 +241,10 @@ struct ScenePainter : BandPart<kBand> {
         if (c > 0) seams |= (unsigned)first << (8 + 6 * (c - 1));
         first += __builtin_amdgcn_readlane(n, c * per) - 1;
       }
-      sftd::raster<8, true>(tc(), q, valid, 0, sftd::kKindRing, 191, band(kYellow, seams));
+      sftd::raster<16, true>(tc(), q, valid, 0, sftd::kKindRing, 191, band(kYellow, seams));
     } else {
       const int m0 = __builtin_amdgcn_readfirstlane(n - 1);  // (lane 0 flattened the first half)
-      sftd::raster<8>(tc(), q, valid, 0, sftd::kKindRing | (m0 << 8), 191);
+      sftd::raster<16>(tc(), q, valid, 0, sftd::kKindRing | (m0 << 8), 191);
     }
   }
   // the score (drawScore, SRC/draw.cpp:161-173): "%07d", grey .5 through the coverage of this geometry's glyph atlas

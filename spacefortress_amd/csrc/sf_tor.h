@@ -77,7 +77,10 @@ SFT_HD double trunc_div(double a, double b) { return a >= 0.0 ? floor_div(a, b) 
 // ---- coverage -> pixel ---------------------------------------------------------------------------------------------------
 SFT_HD int area_to_alpha(int c) {
   const int a = (c + (c << 4) + 256) >> 9;
-  return a > 255 ? 255 : (a < 0 ? 0 : a);
+  // a span's coverage is a uint8_t (cairo_half_open_span_t): where the strokes of one polygon overlap inside a pixel the row's
+  // sums can pass a full cell by a few units, GRID_AREA_TO_ALPHA gives 256 and cairo stores 0 -- a hole in the stroke, drawn
+  // here as cairo draws it (tests/test_view_edges_model.py: the ship at heading 305, .77 x .5 pixels per unit, line width 4.5)
+  return a < 0 ? 0 : (a & 255);
 }
 SFT_HD int mul8(int a, int b) {  // cairo-image-compositor.c mul8x2_8 on one channel: + 0x7f, not pixman's + 0x80
   const int t = a * b + 0x7f;

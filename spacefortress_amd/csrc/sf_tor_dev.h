@@ -174,8 +174,13 @@ __device__ __forceinline__ unsigned band_sources(int okind, unsigned seams) {
   return m;
 }
 
-// MAXACT: how many quads of one object a pixel row taken whole may hold (4: lines; 8: a circle at a large scale -- more and the
-// row is sampled in sub-rows instead, which cairo does not do: the general kernel's circles stay below)
+// MAXACT: how many quads of one object a pixel row taken whole may hold (4: lines; 16: a circle -- the rows through the top and
+// the bottom of its stroke hold the more pieces the wider the line is against the radius: 2 at line width 2 and 1.0 pixel per
+// unit, 8 at 3, 10 at 4.5 there and at .75, 12 at 6, 14 at 9 and at 20, 16 at 13 -- counted on the host over every 1/97 pixel
+// of the centre at scales .5, .75, .8 and 1.0.  MEASURED, not a bound: 16 is known to suffice for line widths up to 20 user
+// units at those scales, and is tested on the device up to 4.5, the widest the reference's front-ends use; a row that holds
+// more falls back to sub-rows, which cairo does not do there, so a wider line than that may be a few levels off at the
+// circle's top and bottom rows: tests/test_gpu_view_edges.py's wide circles)
 template <int MAXACT = 4, bool kBand = false>
 __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool valid, int obj0, int kind, int grey, const Band& band = Band{}) {
   if (SFTD_STOP == 0) return;
@@ -310,6 +315,18 @@ __device__ __forceinline__ void raster(const Ctx& C, const sft::Quad& mine, bool
       for (int v = 0; v < 4; v++) {
         gy[v] = sft::to_grid_y(rv.vy(v));
         full &= !(gy[v] > s0 && gy[v] < s0 + sft::kGridY);
+      }
+      // a circle's curves are joined: where one Bezier segment ends and the next begins cairo's inner_join
+      // (cairo-path-stroke-polygon.c) runs the inner contour through the PATH's point, the middle of the face the two end pieces
+      // meet at -- one more vertex of the polygon, and a row that has it inside is no full row
+      if (okind == kKindRing && k < nq - 1) {
+        bool seam;
+        if constexpr (kBand) seam = (band_slots(okind, k, nq, band.seams) & 0xAAu) != 0u;
+        else seam = k == m0 - 1;
+        if (seam) {
+          const int gs = sft::to_grid_y((rv.vy(1) + rv.vy(2)) >> 1);
+          full &= !(gs > s0 && gs < s0 + sft::kGridY);
+        }
       }
       sft::QuadScan qo;
       const bool ho = rv.has_out();
