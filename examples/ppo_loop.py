@@ -27,6 +27,13 @@ it instead of 0 -- one more critic forward per update (DeviceRollout / FrameRoll
 summed over the window, an env that finishes inside it stops there, an image batch draws one frame per action.  Default 1.
 
     python examples/ppo_loop.py --obs image --frame-skip 4 --envs 1024 --steps 32 --iters 5
+
+--device-policy-head: the step between the network and the env -- Categorical(logits).sample(), log_prob, unsqueeze and two
+copies into the rollout, about ten small launches -- becomes ONE launch (PolicyHead, include/sfmi_policy.h): the loop hands the
+network's logits to rollout.step_logits, which draws the actions on the device, writes their log-probabilities straight into the
+rollout and keeps the rows' entropies (the log line prints their mean).  Off by default; the PPO update is the same either way.
+
+    python examples/ppo_loop.py --device-policy-head --envs 4096 --iters 20
 """
 import argparse
 import os
@@ -61,6 +68,11 @@ class ActorCritic(nn.Module):
         h = self.body(obs)
         return torch.distributions.Categorical(logits=self.pi(h)), self.v(h)
 
+    def logits_value(self, obs):
+        """The policy's logits and the value, for rollout.step_logits (--device-policy-head)."""
+        h = self.body(obs)
+        return self.pi(h), self.v(h)
+
 
 class ConvActorCritic(nn.Module):
     """A small stand-in for rl/model.py's CNN branch: [B, 4, 84, 84] float (0 .. 255) -> policy, value."""
@@ -75,6 +87,10 @@ class ConvActorCritic(nn.Module):
         h = self.body(obs * (1.0 / 255.0))
         return torch.distributions.Categorical(logits=self.pi(h)), self.v(h)
 
+    def logits_value(self, obs):
+        h = self.body(obs * (1.0 / 255.0))
+        return self.pi(h), self.v(h)
+
 
 def main_image(a):
     """The image path: FrameRollout instead of DeviceRollout(env, T, num_stack=4); no `observations` tensor anywhere."""
@@ -88,6 +104,11 @@ def main_image(a):
     t0 = time.perf_counter()
     for it in range(a.iters):
         for t in range(a.steps):
+            if a.device_policy_head:
+                with torch.no_grad():
+                    logits, value = net.logits_value(cur.float())
+                cur, _, _ = ro.step_logits(t, logits, value_pred=value)
+                continue
             with torch.no_grad():
                 dist, value = net(cur.float())
                 action = dist.sample()
@@ -115,6 +136,9 @@ def main_image(a):
             print("iter %3d  env-steps %9d  %.3g env-steps/s (whole loop)  mean final reward %.3f  kills %d" % (
                 it + 1, (it + 1) * a.steps * a.envs, (it + 1) * a.steps * a.envs / dt, float(ro.final_rewards.mean()),
                 ro.num_destruction))
+            if a.device_policy_head:
+                print("          policy head: mean entropy %.4f over the last step's rows, bad rows %d" % (
+                    float(ro.policy_entropy.mean()), ro.policy.check()))
     env.close()
 
 
@@ -132,6 +156,8 @@ def main():
                     help="bootstrap the returns at an episode's end with V(final observation / final frame stack) instead of 0")
     ap.add_argument("--frame-skip", type=int, default=1, metavar="K",
                     help="ticks every action is played for, in one launch (1: a tick per step)")
+    ap.add_argument("--device-policy-head", action="store_true",
+                    help="draw the actions from the network's logits in one launch on the device (rollout.step_logits)")
     a = ap.parse_args()
     torch.manual_seed(0)
     if a.obs == "image":
@@ -148,6 +174,11 @@ def main():
     t0 = time.perf_counter()
     for it in range(a.iters):
         for t in range(a.steps):
+            if a.device_policy_head:
+                with torch.no_grad():
+                    logits, value = net.logits_value(ro.observations[t])
+                ro.step_logits(t, logits, value_pred=value)
+                continue
             with torch.no_grad():
                 dist, value = net(ro.observations[t])
                 action = dist.sample()
@@ -175,6 +206,9 @@ def main():
             print("iter %3d  env-steps %9d  %.3g env-steps/s (whole loop)  mean final reward %.3f  kills %d" % (
                 it + 1, (it + 1) * a.steps * a.envs, (it + 1) * a.steps * a.envs / dt, float(ro.final_rewards.mean()),
                 ro.num_destruction))
+            if a.device_policy_head:
+                print("          policy head: mean entropy %.4f over the last step's rows, bad rows %d" % (
+                    float(ro.policy_entropy.mean()), ro.policy.check()))
             print("          " + reward_line(envs.venv, log))
     envs.close()
 

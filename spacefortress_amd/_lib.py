@@ -195,6 +195,13 @@ FINAL_SYMBOLS = {
     "sf_final_stack_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
+# every symbol include/sfmi_policy.h declares (the policy head): bound like SYMBOLS
+POLICY_SYMBOLS = {
+    "sf_policy_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+POLICY_SAMPLE, POLICY_ARGMAX, POLICY_MAX_ACTIONS = 0, 1, 32  # SF_POLICY_* (sfmi_policy.h)
+
 # what the wrappers answer to `.reset_lanes`: their per-env memory would go stale behind a masked reset
 NO_RESET_LANES = ("%s has no reset_lanes(): its per-env memory (frame stacks, return accumulators, start flags, masks) has no "
                   "rule for a masked reset yet.  Call SFVecEnv.reset_lanes on the bare env and rebuild the wrapper's state, or "
@@ -213,7 +220,7 @@ def lib():
                 "(there is no CPU fallback)" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(MASKED_SYMBOLS.items()) + list(REPEAT_SYMBOLS.items()) \
-                + list(HOLD_SYMBOLS.items()) + list(FINAL_SYMBOLS.items()):
+                + list(HOLD_SYMBOLS.items()) + list(FINAL_SYMBOLS.items()) + list(POLICY_SYMBOLS.items()):
             if not hasattr(L, name) and os.environ.get("SFMI_LIB_PATH"):
                 continue  # an older diagnostic build (A/B against an earlier round's library): entry points added since
             f = getattr(L, name)

@@ -80,6 +80,7 @@ class DeviceRollout:
         self._done = torch.empty(n, dtype=torch.uint8, device=dev)
         self._info = torch.empty(n, dtype=torch.uint8, device=dev)
         self._ptr = None
+        self.policy = None  # the PolicyHead of step_logits, made on its first call (or by seed_policy)
 
     def __getattr__(self, name):
         if name == "reset_lanes":  # (not forwarded to the env: see _lib.NO_RESET_LANES)
@@ -159,6 +160,32 @@ class DeviceRollout:
         if state is not None:
             self.states[step + 1].copy_(state)
         return self._views[step]
+
+    def _policy_head(self):
+        """The rollout's PolicyHead (policy.py), made on first use from the env's n_actions, with what it writes per step: the
+        actions [N] uint8 that the step then plays, `policy_entropy` [N], and the rows of action_log_probs."""
+        if self.policy is None:
+            from .policy import PolicyHead
+            e = self.env
+            self.policy = PolicyHead(e.num_envs, e.n_actions, device=e.device)
+            self._policy_actions = torch.zeros(e.num_envs, dtype=torch.uint8, device=e.device)
+            self.policy_entropy = torch.zeros(e.num_envs, device=e.device)
+            self._logp_rows = [self.action_log_probs[t] for t in range(self.num_steps)]
+        return self.policy
+
+    def seed_policy(self, seed, first_lane=0):
+        """Restart the policy head's stream (PolicyHead.seed): `first_lane` is the global index of this rollout's env 0."""
+        self._policy_head().seed(seed, first_lane)
+
+    def step_logits(self, step, logits, value_pred=None, state=None, deterministic=False):
+        """step() on the policy's logits [N, n_actions] instead of an action: ONE launch (sfmi_policy.h: sf_policy_sample) draws
+        every env's action from its row -- deterministic=True: takes the first maximum -- and writes the log-probabilities
+        straight into action_log_probs[step]; the rows' entropies are in `self.policy_entropy` [N] until the next call.  Then
+        step() with those actions, in every configuration it serves; returns what it returns.  `self.policy` is the head
+        (check() counts the rows that held a NaN, a +inf or nothing but -inf; they play action 0)."""
+        head = self._policy_head()
+        head.sample(logits, deterministic=deterministic, out=(self._policy_actions, self._logp_rows[step], self.policy_entropy))
+        return self.step(step, self._policy_actions, value_pred=value_pred, state=state)
 
     def _record(self, fn, rew, done, ap, at, step, stream):
         """The trainer's float32 bookkeeping as a launch of its own (sf_record_step on the engine's int reward at `rew`,
