@@ -31,7 +31,10 @@ summed over the window, an env that finishes inside it stops there, an image bat
 --device-policy-head: the step between the network and the env -- Categorical(logits).sample(), log_prob, unsqueeze and two
 copies into the rollout, about ten small launches -- becomes ONE launch (PolicyHead, include/sfmi_policy.h): the loop hands the
 network's logits to rollout.step_logits, which draws the actions on the device, writes their log-probabilities straight into the
-rollout and keeps the rows' entropies (the log line prints their mean).  Off by default; the PPO update is the same either way.
+rollout and keeps the rows' entropies (the log line prints their mean).  The PPO update then runs its loss head on the device
+as well: ppo_loss (include/sfmi_ppo.h) evaluates the minibatch's actions with the sampling head's own arithmetic, builds the
+clipped surrogate, the value loss and the entropy bonus in two launches and their gradients in one, and the log line prints the
+last minibatch's losses.  Off by default: without the flag the loop is torch.distributions all the way.
 
     python examples/ppo_loop.py --device-policy-head --envs 4096 --iters 20
 """
@@ -44,7 +47,7 @@ import torch
 import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from spacefortress_amd import DeviceRollout, FrameRollout, SFVecEnv, SFVecNormalize  # noqa: E402
+from spacefortress_amd import DeviceRollout, FrameRollout, SFVecEnv, SFVecNormalize, ppo_loss  # noqa: E402
 from spacefortress_amd.stats import summarize  # noqa: E402
 
 
@@ -56,6 +59,19 @@ def reward_line(venv, log):
         return "no episode finished yet"
     return "mean/median reward %.1f/%.1f, min/max reward %.1f/%.1f over %d episodes" % (
         s["mean_return"], s["median_return"], s["min_return"], s["max_return"], s["episodes"])
+
+
+def device_update(net, opt, obs, act, ret, old_logp, adv_t):
+    """One minibatch of the PPO update with the loss head on the device (--device-policy-head): the network's logits and values
+    go to ppo_loss -- evaluate the actions, the clipped surrogate, the three means and the weighted sum in two launches, their
+    gradients in one (include/sfmi_ppo.h) -- where the default path below runs torch.distributions and a dozen small kernels
+    each way.  -> (loss, policy loss, value loss, entropy), on the device."""
+    logits, value = net.logits_value(obs)
+    losses = ppo_loss(logits, value, act, old_logp, adv_t, ret, 0.1, 0.5, 0.01)
+    opt.zero_grad()
+    losses[0].backward()
+    opt.step()
+    return losses
 
 
 class ActorCritic(nn.Module):
@@ -122,6 +138,9 @@ def main_image(a):
         adv = (adv - adv.mean()) / (adv.std() + 1e-5)
         for _ in range(a.ppo_epochs):
             for obs, _, act, ret, _, old_logp, adv_t in ro.feed_forward_generator(adv, a.mini_batches, obs_dtype=torch.float32):
+                if a.device_policy_head:
+                    losses = device_update(net, opt, obs, act, ret, old_logp, adv_t)
+                    continue
                 dist, value = net(obs)
                 ratio = torch.exp(dist.log_prob(act.squeeze(1)).unsqueeze(1) - old_logp)
                 loss = (-torch.min(ratio * adv_t, torch.clamp(ratio, 0.9, 1.1) * adv_t).mean()
@@ -139,6 +158,8 @@ def main_image(a):
             if a.device_policy_head:
                 print("          policy head: mean entropy %.4f over the last step's rows, bad rows %d" % (
                     float(ro.policy_entropy.mean()), ro.policy.check()))
+                print("          last minibatch: loss %.5f, policy loss %.5f, value loss %.5f, entropy %.5f, bad rows %d" % (
+                    *(float(x) for x in losses), ppo_loss.check()))
     env.close()
 
 
@@ -192,6 +213,9 @@ def main():
         adv = (adv - adv.mean()) / (adv.std() + 1e-5)
         for _ in range(a.ppo_epochs):
             for obs, _, act, ret, _, old_logp, adv_t in ro.feed_forward_generator(adv, a.mini_batches):
+                if a.device_policy_head:
+                    losses = device_update(net, opt, obs, act, ret, old_logp, adv_t)
+                    continue
                 dist, value = net(obs)
                 ratio = torch.exp(dist.log_prob(act.squeeze(1)).unsqueeze(1) - old_logp)
                 loss = (-torch.min(ratio * adv_t, torch.clamp(ratio, 0.9, 1.1) * adv_t).mean()
@@ -209,6 +233,8 @@ def main():
             if a.device_policy_head:
                 print("          policy head: mean entropy %.4f over the last step's rows, bad rows %d" % (
                     float(ro.policy_entropy.mean()), ro.policy.check()))
+                print("          last minibatch: loss %.5f, policy loss %.5f, value loss %.5f, entropy %.5f, bad rows %d" % (
+                    *(float(x) for x in losses), ppo_loss.check()))
             print("          " + reward_line(envs.venv, log))
     envs.close()
 

@@ -202,6 +202,18 @@ POLICY_SYMBOLS = {
 }
 POLICY_SAMPLE, POLICY_ARGMAX, POLICY_MAX_ACTIONS = 0, 1, 32  # SF_POLICY_* (sfmi_policy.h)
 
+# every symbol include/sfmi_ppo.h declares (the policy head's update side: evaluate_actions, the PPO loss): bound like SYMBOLS
+_PPO_IN = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_size_t, C.c_int] + [C.c_float] * 4  # logits .. returns, shape, clip, coefficients
+PPO_SYMBOLS = {
+    "sf_policy_evaluate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "sf_policy_evaluate_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sf_ppo_loss_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "sf_ppo_loss": (C.c_int, _PPO_IN + [C.c_void_p] * 5),
+    "sf_ppo_loss_backward": (C.c_int, _PPO_IN + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+
 # what the wrappers answer to `.reset_lanes`: their per-env memory would go stale behind a masked reset
 NO_RESET_LANES = ("%s has no reset_lanes(): its per-env memory (frame stacks, return accumulators, start flags, masks) has no "
                   "rule for a masked reset yet.  Call SFVecEnv.reset_lanes on the bare env and rebuild the wrapper's state, or "
@@ -220,7 +232,7 @@ def lib():
                 "(there is no CPU fallback)" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(MASKED_SYMBOLS.items()) + list(REPEAT_SYMBOLS.items()) \
-                + list(HOLD_SYMBOLS.items()) + list(FINAL_SYMBOLS.items()) + list(POLICY_SYMBOLS.items()):
+                + list(HOLD_SYMBOLS.items()) + list(FINAL_SYMBOLS.items()) + list(POLICY_SYMBOLS.items()) + list(PPO_SYMBOLS.items()):
             if not hasattr(L, name) and os.environ.get("SFMI_LIB_PATH"):
                 continue  # an older diagnostic build (A/B against an earlier round's library): entry points added since
             f = getattr(L, name)
