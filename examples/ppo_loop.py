@@ -37,6 +37,20 @@ clipped surrogate, the value loss and the entropy bonus in two launches and thei
 last minibatch's losses.  Off by default: without the flag the loop is torch.distributions all the way.
 
     python examples/ppo_loop.py --device-policy-head --envs 4096 --iters 20
+
+--device-minibatches: the stretch between compute_returns and the loss on the device as well (include/sfmi_minibatch.h): the
+normalised advantages are rollout.advantages() -- three launches with a fixed arithmetic instead of six of torch's -- and every
+minibatch is ONE gather launch into buffers that are made once (rollout.minibatches(..., reuse=True)) instead of seven indexing
+launches into fresh tensors.
+
+    python examples/ppo_loop.py --device-policy-head --device-minibatches --envs 4096 --iters 20
+
+--graph-update (features only; implies the two flags above): one minibatch update -- MiniBatcher.next() -> the network ->
+ppo_loss -> backward -> Adam(capturable=True) -- is captured in a graph once and replayed ppo_epochs x mini_batches times per
+iteration, with a shuffle() between epochs.  The batcher's cursor lives on the device, so every replay of the one captured
+gather yields the next minibatch.
+
+    python examples/ppo_loop.py --graph-update --envs 4096 --iters 20
 """
 import argparse
 import os
@@ -72,6 +86,43 @@ def device_update(net, opt, obs, act, ret, old_logp, adv_t):
     losses[0].backward()
     opt.step()
     return losses
+
+
+class GraphUpdate:
+    """--graph-update: one minibatch update as a captured graph.  The first three updates run eagerly on a side stream (torch's
+    warm-up recipe: the optimiser's state and ppo_loss's workspace come to exist there), the fourth call captures one update
+    and every call from then on replays it.  `losses` are the four 0-dim tensors the graph writes."""
+
+    def __init__(self, net, opt, batcher, warmup=3):
+        self.net, self.opt, self.batcher, self.warmup = net, opt, batcher, warmup
+        self.graph, self.losses, self.calls = None, None, 0
+
+    def _update(self):
+        obs, _, act, ret, _, old_logp, adv_t = self.batcher.next()
+        logits, value = self.net.logits_value(obs)
+        losses = ppo_loss(logits, value, act, old_logp, adv_t, ret, 0.1, 0.5, 0.01)
+        self.opt.zero_grad(set_to_none=True)
+        losses[0].backward()
+        self.opt.step()
+        return losses
+
+    def step(self):
+        self.calls += 1
+        if self.graph is not None:
+            self.graph.replay()
+        elif self.calls <= self.warmup:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self.losses = self._update()
+            torch.cuda.current_stream().wait_stream(side)
+        else:
+            self.opt.zero_grad(set_to_none=True)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.losses = self._update()
+            self.graph.replay()  # (capturing launched nothing: this is the update itself)
+        return self.losses
 
 
 class ActorCritic(nn.Module):
@@ -134,10 +185,17 @@ def main_image(a):
             # the critic's value of every env's final stack: used where masks == 0 only
             final_value = net(ro.final_obs().float())[1] if a.time_limit_bootstrap else None
         ro.compute_returns(next_value, True, 0.99, 0.95, final_value=final_value)
-        adv = ro.returns[:-1] - ro.value_preds[:-1]
-        adv = (adv - adv.mean()) / (adv.std() + 1e-5)
+        if a.device_minibatches:
+            adv = ro.advantages()
+        else:
+            adv = ro.returns[:-1] - ro.value_preds[:-1]
+            adv = (adv - adv.mean()) / (adv.std() + 1e-5)
         for _ in range(a.ppo_epochs):
-            for obs, _, act, ret, _, old_logp, adv_t in ro.feed_forward_generator(adv, a.mini_batches, obs_dtype=torch.float32):
+            if a.device_minibatches:
+                batches = ro.minibatches(adv, a.mini_batches, reuse=True, obs_dtype=torch.float32)
+            else:
+                batches = ro.feed_forward_generator(adv, a.mini_batches, obs_dtype=torch.float32)
+            for obs, _, act, ret, _, old_logp, adv_t in batches:
                 if a.device_policy_head:
                     losses = device_update(net, opt, obs, act, ret, old_logp, adv_t)
                     continue
@@ -160,6 +218,8 @@ def main_image(a):
                     float(ro.policy_entropy.mean()), ro.policy.check()))
                 print("          last minibatch: loss %.5f, policy loss %.5f, value loss %.5f, entropy %.5f, bad rows %d" % (
                     *(float(x) for x in losses), ppo_loss.check()))
+            if a.device_minibatches and not a.device_policy_head:
+                print("          last minibatch: loss %.5f" % float(loss))
     env.close()
 
 
@@ -179,7 +239,18 @@ def main():
                     help="ticks every action is played for, in one launch (1: a tick per step)")
     ap.add_argument("--device-policy-head", action="store_true",
                     help="draw the actions from the network's logits in one launch on the device (rollout.step_logits)")
+    ap.add_argument("--device-minibatches", action="store_true",
+                    help="normalised advantages in three launches, every minibatch one gather launch into reused buffers")
+    ap.add_argument("--graph-update", action="store_true",
+                    help="capture one minibatch update (gather, network, ppo_loss, backward, Adam) once and replay it; features "
+                         "only; implies --device-policy-head --device-minibatches")
     a = ap.parse_args()
+    if a.graph_update:
+        if a.obs == "image":
+            ap.error("--graph-update is for --obs features")
+        if (a.steps * a.envs) % a.mini_batches:
+            ap.error("--graph-update needs minibatches of equal size: steps * envs must be a multiple of --mini-batches")
+        a.device_policy_head = a.device_minibatches = True
     torch.manual_seed(0)
     if a.obs == "image":
         if a.time_limit_bootstrap and a.frame_skip > 1:
@@ -189,8 +260,10 @@ def main():
     log = envs.venv.enable_episode_log()
     ro = DeviceRollout(envs, a.steps, time_limit_bootstrap=a.time_limit_bootstrap)
     net = ActorCritic(envs.venv.obs_dim, envs.venv.n_actions).to(envs.device)
-    opt = torch.optim.Adam(net.parameters(), lr=7e-4)
+    opt = torch.optim.Adam(net.parameters(), lr=7e-4, capturable=a.graph_update)
     ro.reset()
+    adv_buf = torch.zeros(a.steps, a.envs, 1, device=envs.device) if a.device_minibatches else None  # filled in place per update
+    graph = GraphUpdate(net, opt, ro.batcher(adv_buf, a.mini_batches)) if a.graph_update else None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(a.iters):
@@ -209,10 +282,22 @@ def main():
             # the critic's value of every env's final observation (normalised like the rest): used where masks == 0 only
             final_value = net(ro.final_obs())[1] if a.time_limit_bootstrap else None
         ro.compute_returns(next_value, True, 0.99, 0.95, final_value=final_value)
-        adv = ro.returns[:-1] - ro.value_preds[:-1]
-        adv = (adv - adv.mean()) / (adv.std() + 1e-5)
+        if a.device_minibatches:
+            adv = ro.advantages(out=adv_buf)
+        else:
+            adv = ro.returns[:-1] - ro.value_preds[:-1]
+            adv = (adv - adv.mean()) / (adv.std() + 1e-5)
         for _ in range(a.ppo_epochs):
-            for obs, _, act, ret, _, old_logp, adv_t in ro.feed_forward_generator(adv, a.mini_batches):
+            if graph is not None:  # the captured update, once per minibatch; the cursor moves on the device
+                graph.batcher.shuffle()
+                for _ in range(a.mini_batches):
+                    losses = graph.step()
+                continue
+            if a.device_minibatches:
+                batches = ro.minibatches(adv, a.mini_batches, reuse=True)
+            else:
+                batches = ro.feed_forward_generator(adv, a.mini_batches)
+            for obs, _, act, ret, _, old_logp, adv_t in batches:
                 if a.device_policy_head:
                     losses = device_update(net, opt, obs, act, ret, old_logp, adv_t)
                     continue
@@ -235,6 +320,11 @@ def main():
                     float(ro.policy_entropy.mean()), ro.policy.check()))
                 print("          last minibatch: loss %.5f, policy loss %.5f, value loss %.5f, entropy %.5f, bad rows %d" % (
                     *(float(x) for x in losses), ppo_loss.check()))
+            if a.device_minibatches and not a.device_policy_head:
+                print("          last minibatch: loss %.5f" % float(loss))
+            if graph is not None:
+                print("          graph update: %d minibatch updates, %d of them replays of the one captured update" % (
+                    graph.calls, max(0, graph.calls - graph.warmup)))
             print("          " + reward_line(envs.venv, log))
     envs.close()
 

@@ -7,7 +7,7 @@ environment does, and fails loudly if the extension or the device is missing.
 """
 from ._lib import SfmiError, lib  # noqa: F401
 
-__all__ = ["SFVecEnv", "SSF_Env", "FrameStack", "SFVecNormalize", "DeviceRollout", "FrameRollout", "EpisodeLog", "PolicyHead", "evaluate_actions", "ppo_loss", "Replay", "LaneStates", "SfmiError", "lib"]
+__all__ = ["SFVecEnv", "SSF_Env", "FrameStack", "SFVecNormalize", "DeviceRollout", "FrameRollout", "EpisodeLog", "PolicyHead", "evaluate_actions", "ppo_loss", "MiniBatcher", "Replay", "LaneStates", "SfmiError", "lib"]
 
 
 def __getattr__(name):
@@ -41,6 +41,9 @@ def __getattr__(name):
     if name in ("evaluate_actions", "ppo_loss"):
         from . import policy
         return getattr(policy, name)
+    if name == "MiniBatcher":
+        from .minibatch import MiniBatcher
+        return MiniBatcher
     if name == "Replay":
         from .replay import Replay
         return Replay

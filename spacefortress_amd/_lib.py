@@ -214,6 +214,22 @@ PPO_SYMBOLS = {
     "sf_ppo_loss_backward": (C.c_int, _PPO_IN + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
+# every symbol include/sfmi_minibatch.h declares (normalised advantages, one-launch minibatch gathers): bound like SYMBOLS
+MB_MAX_COLUMNS, MB_MAX_ROW_BYTES = 8, 65536  # SF_MB_* (sfmi_minibatch.h)
+
+
+class MbColumn(C.Structure):
+    """sf_mb_column (include/sfmi_minibatch.h): one column of a minibatch gather"""
+    _fields_ = [("src_dev", C.c_void_p), ("row_bytes", C.c_size_t), ("dst_dev", C.c_void_p)]
+
+
+MINIBATCH_SYMBOLS = {
+    "sf_advantages_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "sf_advantages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double] + [C.c_void_p] * 5),
+    "sf_minibatch_gather": (C.c_int, [C.POINTER(MbColumn), C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p,
+                                      C.c_uint32, C.c_uint32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 # what the wrappers answer to `.reset_lanes` (INTEGRATION.md): their per-env memory would go stale behind a masked reset
 NO_RESET_LANES = ("%s has no reset_lanes(): its per-env memory (frame stacks, return accumulators, start flags, masks) has no "
                   "rule for a masked reset yet.  Call SFVecEnv.reset_lanes on the bare env and rebuild the wrapper's state, or "
@@ -232,7 +248,8 @@ def lib():
                 "(there is no CPU fallback)" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(MASKED_SYMBOLS.items()) + list(REPEAT_SYMBOLS.items()) \
-                + list(HOLD_SYMBOLS.items()) + list(FINAL_SYMBOLS.items()) + list(POLICY_SYMBOLS.items()) + list(PPO_SYMBOLS.items()):
+                + list(HOLD_SYMBOLS.items()) + list(FINAL_SYMBOLS.items()) + list(POLICY_SYMBOLS.items()) + list(PPO_SYMBOLS.items()) \
+                + list(MINIBATCH_SYMBOLS.items()):
             if not hasattr(L, name) and os.environ.get("SFMI_LIB_PATH"):
                 continue  # an older diagnostic build (A/B against an earlier round's library): entry points added since
             f = getattr(L, name)

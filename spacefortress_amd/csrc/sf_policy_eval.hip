@@ -17,6 +17,7 @@
 // Nothing here is bound by anything but launch latency (327 680 x 5 floats = 6.5 MB); there is no LDS in the row passes.
 #include <hip/hip_runtime.h>
 
+#include "sf_fixed_sum.h"
 #include "sf_internal.h"
 #include "sfmi_ppo.h"
 
@@ -178,45 +179,17 @@ __global__ __launch_bounds__(256) void sf_ppo_loss_kernel(const float* __restric
     row_terms[3 * i + 2] = H;
   }
   sf_count_bad(live && R.bad, bad_rows);
-  double vs = live ? (double)s : 0.0, vq = live ? (double)q : 0.0, vh = live ? (double)H : 0.0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {  // the fixed tree: every lane ends with the wave's sum, lane 0's is the one kept
-    vs = vs + __shfl_xor(vs, off);
-    vq = vq + __shfl_xor(vq, off);
-    vh = vh + __shfl_xor(vh, off);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    part[wave][0] = vs;
-    part[wave][1] = vq;
-    part[wave][2] = vh;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int j = threadIdx.x;
-    double t = part[0][j];
-    t = t + part[1][j];
-    t = t + part[2][j];
-    t = t + part[3][j];
-    partials[(size_t)blockIdx.x * 3 + j] = t;
-  }
+  // the fixed order (sf_fixed_sum.h): the tree in the wave, the block's four waves and then the blocks in index order
+  double v[3] = {live ? (double)s : 0.0, live ? (double)q : 0.0, live ? (double)H : 0.0};
+  sf_block_partials<3>(v, part, partials);
 }
 
-#define SF_PPO_FINISH_CHUNK 1024
 __global__ __launch_bounds__(256) void sf_ppo_finish_kernel(const double* __restrict__ partials, int nblocks, int n, float value_coef,
                                                             float entropy_coef, float* __restrict__ sums) {
-  __shared__ double buf[SF_PPO_FINISH_CHUNK * 3];
+  __shared__ double buf[SF_SUM_CHUNK * 3];
   __shared__ double tot[3];
   const int tid = threadIdx.x;
-  double acc = 0.0;
-  for (int base = 0; base < nblocks; base += SF_PPO_FINISH_CHUNK) {
-    const int blocks = nblocks - base < SF_PPO_FINISH_CHUNK ? nblocks - base : SF_PPO_FINISH_CHUNK;
-    for (int j = tid; j < blocks * 3; j += 256) buf[j] = partials[(size_t)base * 3 + j];
-    __syncthreads();
-    if (tid < 3)
-      for (int b = 0; b < blocks; b++) acc = acc + buf[b * 3 + tid];  // the blocks in index order
-    __syncthreads();
-  }
+  const double acc = sf_blocks_in_order<3>(partials, nblocks, buf);
   if (tid < 3) tot[tid] = acc;
   __syncthreads();
   if (tid == 0) {

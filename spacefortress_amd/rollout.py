@@ -273,6 +273,37 @@ class DeviceRollout:
         self.states[0].copy_(self.states[-1])
         self.masks[0].copy_(self.masks[-1])
 
+    # ------------------------------------------------------------------ advantages and minibatches on the device
+    def advantages(self, eps=1e-5, out=None):
+        """rl/train.py:107-108 -- returns[:-1] - value_preds[:-1], minus its mean, over its unbiased std + eps -- as [T, n, 1]
+        float32 in three launches with a fixed arithmetic (sfmi_minibatch.h: sf_advantages; float64 sums in a fixed order: equal
+        inputs give equal bits).  `out`: a contiguous float32 tensor of T n elements to fill in place.  `self.advantage_stats`
+        holds the mean and the std as two doubles on the device.  Nothing synchronises."""
+        T, n = self.rewards.shape[0:2]
+        M, dev = T * n, self.env.device
+        if out is None:
+            out = torch.empty(T, n, 1, dtype=torch.float32, device=dev)
+        elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == M):
+            raise ValueError("advantages: out must be a contiguous float32 tensor of %d elements on %s" % (M, dev))
+        if self.__dict__.get("advantage_stats") is None:
+            self.advantage_stats = torch.zeros(2, dtype=torch.float64, device=dev)
+            self._adv_ws = torch.empty(max(1, int(self._L.sf_advantages_workspace_bytes(M)) // 8), dtype=torch.float64, device=dev)
+        _lib.check(self._L.sf_advantages(ptr(self.returns), ptr(self.value_preds), M, float(eps), ptr(out), None,
+                                         ptr(self.advantage_stats), ptr(self._adv_ws), self._stream()))
+        return out.view(T, n, 1)
+
+    def batcher(self, advantages, num_mini_batch, recurrent=False, obs_dtype=None):
+        """A MiniBatcher (minibatch.py) over this rollout: fixed minibatch buffers, the permutation and the cursor on the
+        device; next() is one gather launch and can be captured in a graph."""
+        from .minibatch import MiniBatcher
+        return MiniBatcher(self, advantages, num_mini_batch, recurrent=recurrent, obs_dtype=obs_dtype)
+
+    def minibatches(self, advantages, num_mini_batch, recurrent=False, perm=None, reuse=False, obs_dtype=None):
+        """feed_forward_generator / recurrent_generator with one gather launch per minibatch (minibatch.py: minibatches): the
+        same tuple, with the same `perm` the same bits; reuse=True yields the same buffers every time."""
+        from .minibatch import minibatches
+        return minibatches(self, advantages, num_mini_batch, recurrent=recurrent, perm=perm, reuse=reuse, obs_dtype=obs_dtype)
+
     # ------------------------------------------------------------------ PPO sampling (rl/storage.py:66-122)
     def feed_forward_generator(self, advantages, num_mini_batch):
         """Random minibatches over the T x N transitions; same tuple and shapes as the reference's generator."""
