@@ -51,6 +51,16 @@ iteration, with a shuffle() between epochs.  The batcher's cursor lives on the d
 gather yields the next minibatch.
 
     python examples/ppo_loop.py --graph-update --envs 4096 --iters 20
+
+--max-grad-norm X: the reference's clip_grad_norm_(parameters, X) between backward() and the optimiser's step (rl/train.py:131)
+on every path.  Default 0: no clipping, as before.
+
+--device-optimizer: DeviceAdam (include/sfmi_optim.h) in place of torch.optim.Adam on every path: the norm, the clipping and
+the Adam step for all parameters in three launches, the step count and a skipped step kept on the device; --max-grad-norm goes
+to it instead of clip_grad_norm_.  Its step() is capturable as it is, so --graph-update takes it unchanged.  The log line prints
+the last gradient norm and the count of steps skipped for a non-finite gradient.
+
+    python examples/ppo_loop.py --graph-update --device-optimizer --max-grad-norm 0.5 --envs 4096 --iters 20
 """
 import argparse
 import os
@@ -61,7 +71,7 @@ import torch
 import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from spacefortress_amd import DeviceRollout, FrameRollout, SFVecEnv, SFVecNormalize, ppo_loss  # noqa: E402
+from spacefortress_amd import DeviceAdam, DeviceRollout, FrameRollout, SFVecEnv, SFVecNormalize, ppo_loss  # noqa: E402
 from spacefortress_amd.stats import summarize  # noqa: E402
 
 
@@ -75,7 +85,25 @@ def reward_line(venv, log):
         s["mean_return"], s["median_return"], s["min_return"], s["max_return"], s["episodes"])
 
 
-def device_update(net, opt, obs, act, ret, old_logp, adv_t):
+def make_optimizer(a, net, capturable=False):
+    """torch.optim.Adam, or with --device-optimizer DeviceAdam, which clips inside its step."""
+    if a.device_optimizer:
+        return DeviceAdam(net.parameters(), lr=7e-4, max_grad_norm=a.max_grad_norm if a.max_grad_norm > 0 else None)
+    return torch.optim.Adam(net.parameters(), lr=7e-4, capturable=capturable)
+
+
+def optimizer_step(opt, max_grad_norm):
+    """rl/train.py:131-132: clip_grad_norm_ where asked for (DeviceAdam has it inside), then the step."""
+    if max_grad_norm > 0 and not isinstance(opt, DeviceAdam):
+        torch.nn.utils.clip_grad_norm_([p for g in opt.param_groups for p in g["params"]], max_grad_norm)
+    opt.step()
+
+
+def optimizer_line(opt):
+    return "          device optimizer: last grad norm %.4f, coef %.4f, skipped steps %d" % (opt.last_norm(), opt.last_coef(), opt.check())
+
+
+def device_update(net, opt, obs, act, ret, old_logp, adv_t, max_grad_norm=0.0):
     """One minibatch of the PPO update with the loss head on the device (--device-policy-head): the network's logits and values
     go to ppo_loss -- evaluate the actions, the clipped surrogate, the three means and the weighted sum in two launches, their
     gradients in one (include/sfmi_ppo.h) -- where the default path below runs torch.distributions and a dozen small kernels
@@ -84,7 +112,7 @@ def device_update(net, opt, obs, act, ret, old_logp, adv_t):
     losses = ppo_loss(logits, value, act, old_logp, adv_t, ret, 0.1, 0.5, 0.01)
     opt.zero_grad()
     losses[0].backward()
-    opt.step()
+    optimizer_step(opt, max_grad_norm)
     return losses
 
 
@@ -93,8 +121,8 @@ class GraphUpdate:
     warm-up recipe: the optimiser's state and ppo_loss's workspace come to exist there), the fourth call captures one update
     and every call from then on replays it.  `losses` are the four 0-dim tensors the graph writes."""
 
-    def __init__(self, net, opt, batcher, warmup=3):
-        self.net, self.opt, self.batcher, self.warmup = net, opt, batcher, warmup
+    def __init__(self, net, opt, batcher, warmup=3, max_grad_norm=0.0):
+        self.net, self.opt, self.batcher, self.warmup, self.max_grad_norm = net, opt, batcher, warmup, max_grad_norm
         self.graph, self.losses, self.calls = None, None, 0
 
     def _update(self):
@@ -103,7 +131,7 @@ class GraphUpdate:
         losses = ppo_loss(logits, value, act, old_logp, adv_t, ret, 0.1, 0.5, 0.01)
         self.opt.zero_grad(set_to_none=True)
         losses[0].backward()
-        self.opt.step()
+        optimizer_step(self.opt, self.max_grad_norm)
         return losses
 
     def step(self):
@@ -164,7 +192,7 @@ def main_image(a):
     env = SFVecEnv(a.envs, gametype=a.gametype, obs_type="image", spawn_stride=1, frame_skip=a.frame_skip)
     ro = FrameRollout(env, a.steps, num_stack=4, time_limit_bootstrap=a.time_limit_bootstrap)
     net = ConvActorCritic(4, env.n_actions).to(env.device)
-    opt = torch.optim.Adam(net.parameters(), lr=7e-4)
+    opt = make_optimizer(a, net)
     cur = ro.reset()
     print("observation storage: %.1f MB (stacked: %.1f MB)" % (ro.nbytes() / 1e6, (a.steps + 1) * a.envs * 4 * 7056 / 1e6))
     torch.cuda.synchronize()
@@ -197,7 +225,7 @@ def main_image(a):
                 batches = ro.feed_forward_generator(adv, a.mini_batches, obs_dtype=torch.float32)
             for obs, _, act, ret, _, old_logp, adv_t in batches:
                 if a.device_policy_head:
-                    losses = device_update(net, opt, obs, act, ret, old_logp, adv_t)
+                    losses = device_update(net, opt, obs, act, ret, old_logp, adv_t, a.max_grad_norm)
                     continue
                 dist, value = net(obs)
                 ratio = torch.exp(dist.log_prob(act.squeeze(1)).unsqueeze(1) - old_logp)
@@ -205,7 +233,7 @@ def main_image(a):
                         + 0.5 * (value - ret).pow(2).mean() - 0.01 * dist.entropy().mean())
                 opt.zero_grad()
                 loss.backward()
-                opt.step()
+                optimizer_step(opt, a.max_grad_norm)
         ro.after_update()  # (the current stack is stack_at(0) of the next rollout: `cur` stays valid)
         if (it + 1) % 5 == 0 or it == a.iters - 1:
             torch.cuda.synchronize()
@@ -220,6 +248,8 @@ def main_image(a):
                     *(float(x) for x in losses), ppo_loss.check()))
             if a.device_minibatches and not a.device_policy_head:
                 print("          last minibatch: loss %.5f" % float(loss))
+            if a.device_optimizer:
+                print(optimizer_line(opt))
     env.close()
 
 
@@ -244,6 +274,10 @@ def main():
     ap.add_argument("--graph-update", action="store_true",
                     help="capture one minibatch update (gather, network, ppo_loss, backward, Adam) once and replay it; features "
                          "only; implies --device-policy-head --device-minibatches")
+    ap.add_argument("--max-grad-norm", type=float, default=0.0, metavar="X",
+                    help="clip_grad_norm_(parameters, X) in front of every optimiser step, as the reference does (0: off)")
+    ap.add_argument("--device-optimizer", action="store_true",
+                    help="DeviceAdam in place of torch.optim.Adam: norm, clipping and the Adam step in three launches")
     a = ap.parse_args()
     if a.graph_update:
         if a.obs == "image":
@@ -260,10 +294,10 @@ def main():
     log = envs.venv.enable_episode_log()
     ro = DeviceRollout(envs, a.steps, time_limit_bootstrap=a.time_limit_bootstrap)
     net = ActorCritic(envs.venv.obs_dim, envs.venv.n_actions).to(envs.device)
-    opt = torch.optim.Adam(net.parameters(), lr=7e-4, capturable=a.graph_update)
+    opt = make_optimizer(a, net, capturable=a.graph_update)
     ro.reset()
     adv_buf = torch.zeros(a.steps, a.envs, 1, device=envs.device) if a.device_minibatches else None  # filled in place per update
-    graph = GraphUpdate(net, opt, ro.batcher(adv_buf, a.mini_batches)) if a.graph_update else None
+    graph = GraphUpdate(net, opt, ro.batcher(adv_buf, a.mini_batches), max_grad_norm=a.max_grad_norm) if a.graph_update else None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(a.iters):
@@ -299,7 +333,7 @@ def main():
                 batches = ro.feed_forward_generator(adv, a.mini_batches)
             for obs, _, act, ret, _, old_logp, adv_t in batches:
                 if a.device_policy_head:
-                    losses = device_update(net, opt, obs, act, ret, old_logp, adv_t)
+                    losses = device_update(net, opt, obs, act, ret, old_logp, adv_t, a.max_grad_norm)
                     continue
                 dist, value = net(obs)
                 ratio = torch.exp(dist.log_prob(act.squeeze(1)).unsqueeze(1) - old_logp)
@@ -307,7 +341,7 @@ def main():
                         + 0.5 * (value - ret).pow(2).mean() - 0.01 * dist.entropy().mean())
                 opt.zero_grad()
                 loss.backward()
-                opt.step()
+                optimizer_step(opt, a.max_grad_norm)
         ro.after_update()
         if (it + 1) % 5 == 0 or it == a.iters - 1:
             torch.cuda.synchronize()
@@ -325,6 +359,8 @@ def main():
             if graph is not None:
                 print("          graph update: %d minibatch updates, %d of them replays of the one captured update" % (
                     graph.calls, max(0, graph.calls - graph.warmup)))
+            if a.device_optimizer:
+                print(optimizer_line(opt))
             print("          " + reward_line(envs.venv, log))
     envs.close()
 

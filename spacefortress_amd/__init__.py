@@ -7,7 +7,7 @@ environment does, and fails loudly if the extension or the device is missing.
 """
 from ._lib import SfmiError, lib  # noqa: F401
 
-__all__ = ["SFVecEnv", "SSF_Env", "FrameStack", "SFVecNormalize", "DeviceRollout", "FrameRollout", "EpisodeLog", "PolicyHead", "evaluate_actions", "ppo_loss", "MiniBatcher", "Replay", "LaneStates", "SfmiError", "lib"]
+__all__ = ["SFVecEnv", "SSF_Env", "FrameStack", "SFVecNormalize", "DeviceRollout", "FrameRollout", "EpisodeLog", "PolicyHead", "evaluate_actions", "ppo_loss", "MiniBatcher", "DeviceAdam", "Replay", "LaneStates", "SfmiError", "lib"]
 
 
 def __getattr__(name):
@@ -44,6 +44,9 @@ def __getattr__(name):
     if name == "MiniBatcher":
         from .minibatch import MiniBatcher
         return MiniBatcher
+    if name == "DeviceAdam":
+        from .optim import DeviceAdam
+        return DeviceAdam
     if name == "Replay":
         from .replay import Replay
         return Replay

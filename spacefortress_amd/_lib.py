@@ -230,6 +230,23 @@ MINIBATCH_SYMBOLS = {
                                       C.c_uint32, C.c_uint32, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# every symbol include/sfmi_optim.h declares (grad-norm clip and Adam, fused): bound like SYMBOLS
+OPT_MAX_TENSORS, OPT_CHUNK, ADAM_STATE_BYTES = 64, 2048, 128  # SF_OPT_* / SF_ADAM_STATE_BYTES (sfmi_optim.h)
+
+
+class OptTensor(C.Structure):
+    """sf_opt_tensor (include/sfmi_optim.h): one tensor of an optimiser step"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_int64)]
+
+
+OPTIM_SYMBOLS = {
+    "sf_adam_chunks": (C.c_int64, [C.c_int64]),
+    "sf_adam_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "sf_adam_state_bytes": (C.c_size_t, []),
+    "sf_adam_state_init": (C.c_int, [C.c_void_p] + [C.c_double] * 4 + [C.c_void_p]),
+    "sf_adam_step": (C.c_int, [C.POINTER(OptTensor), C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 # what the wrappers answer to `.reset_lanes` (INTEGRATION.md): their per-env memory would go stale behind a masked reset
 NO_RESET_LANES = ("%s has no reset_lanes(): its per-env memory (frame stacks, return accumulators, start flags, masks) has no "
                   "rule for a masked reset yet.  Call SFVecEnv.reset_lanes on the bare env and rebuild the wrapper's state, or "
@@ -249,7 +266,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(MASKED_SYMBOLS.items()) + list(REPEAT_SYMBOLS.items()) \
                 + list(HOLD_SYMBOLS.items()) + list(FINAL_SYMBOLS.items()) + list(POLICY_SYMBOLS.items()) + list(PPO_SYMBOLS.items()) \
-                + list(MINIBATCH_SYMBOLS.items()):
+                + list(MINIBATCH_SYMBOLS.items()) + list(OPTIM_SYMBOLS.items()):
             if not hasattr(L, name) and os.environ.get("SFMI_LIB_PATH"):
                 continue  # an older diagnostic build (A/B against an earlier round's library): entry points added since
             f = getattr(L, name)

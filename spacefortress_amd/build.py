@@ -14,8 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsfmi.so")
-SOURCES = ["sf_kernels.hip", "sf_state_ops.hip", "sf_render.hip", "sf_render_generic.hip", "sf_render_view.hip", "sf_normalize.hip", "sf_rollout_ops.hip", "sf_frame_store.hip", "sf_episode_log.hip", "sf_final_frames.hip", "sf_policy.hip", "sf_policy_eval.hip", "sf_minibatch.hip", "sf_capi.cpp", "sf_image_capi.cpp", "sf_state_capi.cpp", "sf_norm_capi.cpp", "sf_eplog_capi.cpp", "sf_final_capi.cpp", "sf_host.cpp", "sf_image.cpp", "sf_cairo_host.cpp", "sf_view_host.cpp"]
-HEADERS = ["sf_layout.h", "sf_lane_dev.h", "sf_events.h", "sf_drawrec.h", "sf_internal.h", "sf_batch.h", "sf_view.h", "sf_raster.h", "sf_tor.h", "sf_tor_dev.h", "sf_scene_dev.h", "sf_generic_frame_dev.h", "sf_cairo_host.h", "sf_deg_dd.h", "sf_glyphs.h", "sf_fixed_sum.h", os.path.join(ROOT, "include", "sfmi.h"), os.path.join(ROOT, "include", "sfmi_final.h"), os.path.join(ROOT, "include", "sfmi_hold.h"), os.path.join(ROOT, "include", "sfmi_masked.h"), os.path.join(ROOT, "include", "sfmi_minibatch.h"), os.path.join(ROOT, "include", "sfmi_policy.h"), os.path.join(ROOT, "include", "sfmi_ppo.h"), os.path.join(ROOT, "include", "sfmi_repeat.h")]
+SOURCES = ["sf_kernels.hip", "sf_state_ops.hip", "sf_render.hip", "sf_render_generic.hip", "sf_render_view.hip", "sf_normalize.hip", "sf_rollout_ops.hip", "sf_frame_store.hip", "sf_episode_log.hip", "sf_final_frames.hip", "sf_policy.hip", "sf_policy_eval.hip", "sf_minibatch.hip", "sf_optim.hip", "sf_capi.cpp", "sf_image_capi.cpp", "sf_state_capi.cpp", "sf_norm_capi.cpp", "sf_eplog_capi.cpp", "sf_final_capi.cpp", "sf_host.cpp", "sf_image.cpp", "sf_cairo_host.cpp", "sf_view_host.cpp"]
+HEADERS = ["sf_layout.h", "sf_lane_dev.h", "sf_events.h", "sf_drawrec.h", "sf_internal.h", "sf_batch.h", "sf_view.h", "sf_raster.h", "sf_tor.h", "sf_tor_dev.h", "sf_scene_dev.h", "sf_generic_frame_dev.h", "sf_cairo_host.h", "sf_deg_dd.h", "sf_glyphs.h", "sf_fixed_sum.h", os.path.join(ROOT, "include", "sfmi.h"), os.path.join(ROOT, "include", "sfmi_final.h"), os.path.join(ROOT, "include", "sfmi_hold.h"), os.path.join(ROOT, "include", "sfmi_masked.h"), os.path.join(ROOT, "include", "sfmi_minibatch.h"), os.path.join(ROOT, "include", "sfmi_optim.h"), os.path.join(ROOT, "include", "sfmi_policy.h"), os.path.join(ROOT, "include", "sfmi_ppo.h"), os.path.join(ROOT, "include", "sfmi_repeat.h")]
 
 
 # -amdgpu-kernarg-preload-count: the first eight kernel parameters (as many as fit the 14 free user SGPRs) arrive in
